@@ -26,6 +26,10 @@ With N>1 ranks, per-GPU work is fixed (weak scaling); GROUP BYs are two-phase ov
     python bench.py                                   # 1 GPU, config 2
     python bench.py --flow window                     # config 3 (warms up 305 steps to fill the 5-min window)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+
+A plain run sets up, warms up, times ``--steps`` micro-batches and prints one JSON line.  ``--full`` adds the
+figures that take a measurement of their own (the host's pinned H2D bandwidth and the step's fraction of it);
+``--dump-outputs DIR`` writes what the sinks received in the last timed step as ``.npy`` files (``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -123,11 +127,79 @@ def sim_gen_args(j: int, rank: int, E: int, clock0_us: int, interval_us: int) ->
                 step_us=max(1, interval_us // E))
 
 
+DUMP_CLOCK0_US = 1_750_000_000 * 1_000_000     # --dump-outputs: the simulated clock starts here in every run
+DUMP_MAX_ROWS = 32768                           # --dump-outputs: rows kept per output (a seeded sample beyond that)
+DUMP_MAX_BYTES = 64_000_000                     # --dump-outputs: all files together
+
+
+def _flatten_doc(doc, prefix, row):
+    """One rendered JSON document as {dotted path: float64}.  Numbers keep their value, booleans are 0/1, null is
+    NaN; strings and arrays become the CRC-32 of their text (exact in a double), so equal text gives equal numbers."""
+    import zlib
+    for k, v in doc.items():
+        path = f"{prefix}{k}"
+        if isinstance(v, dict):
+            _flatten_doc(v, path + ".", row)
+        elif isinstance(v, bool):
+            row[path] = float(v)
+        elif isinstance(v, (int, float)):
+            row[path] = float(v)
+        elif v is None:
+            row[path] = float("nan")
+        else:
+            text = v if isinstance(v, str) else json.dumps(v, sort_keys=True, separators=(",", ":"))
+            row[path] = float(zlib.crc32(text.encode("utf-8")))
+
+
+def dump_outputs(folder, outputs, prefix=""):
+    """``--dump-outputs``: write what the sinks of the last timed batch received.  ``outputs`` is a list of
+    (output name, rendered JSON lines); every leaf field of the documents becomes ``<output>.<field path>.npy``, a
+    float64 vector with one value per row, and ``<output>.rows.npy`` holds the indices of the rows kept (all of
+    them up to DUMP_MAX_ROWS, else a fixed seeded sample in row order).  Returns {file name: rows}."""
+    import re
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    written, budget = {}, DUMP_MAX_BYTES
+
+    def save(name, arr):
+        nonlocal budget
+        if arr.nbytes > budget:
+            raise SystemExit(f"bench.py: --dump-outputs would exceed {DUMP_MAX_BYTES} bytes at {name}")
+        budget -= arr.nbytes
+        fn = re.sub(r"[^A-Za-z0-9_.\-]", "_", prefix + name) + ".npy"
+        np.save(os.path.join(folder, fn), arr)
+        written[fn] = int(arr.shape[0])
+
+    for out_name, lines in outputs:
+        n = len(lines)
+        keep = np.arange(n, dtype=np.int64)
+        if n > DUMP_MAX_ROWS:
+            keep = np.sort(np.random.default_rng(20240607).choice(n, DUMP_MAX_ROWS, replace=False)).astype(np.int64)
+        rows = []
+        for i in keep.tolist():
+            row = {}
+            _flatten_doc(json.loads(lines[i]), "", row)
+            rows.append(row)
+        cols = list(dict.fromkeys(k for row in rows for k in row))
+        save(f"{out_name}.rows", keep.astype(np.float64))
+        for c in cols:
+            save(f"{out_name}.{c}", np.array([row.get(c, float("nan")) for row in rows], dtype=np.float64))
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (micro-batches)")
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: this host's pinned H2D bandwidth on a "
+                         "copy of one step's ingest, measured before the timed steps (h2d_gb_s, ingest_mb_per_step, "
+                         "pcie_fraction in the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the sinks received in the last timed step to DIR as "
+                         "float64 .npy files, one per output field (see dump_outputs); the simulated clock then "
+                         "starts at a fixed time, so the same arguments give the same inputs in every run")
     ap.add_argument("--flow", choices=list(DEFAULT_EVENTS), default="groupby")
     ap.add_argument("--events-per-batch", type=int, default=None, help="events per GPU per micro-batch")
     ap.add_argument("--ref-rows", type=int, default=100_000_000, help="reference table rows (join flow)")
@@ -283,6 +355,10 @@ def main():
     prog = iot.program()
     interval_us = 1_000_000
     clock0_us = (int(time.time()) - 3600) * 1_000_000      # simulated clock, aligned to the interval
+    if args.dump_outputs:
+        # the same inputs in every run: event times (and current_timestamp()) must not follow the wall clock
+        clock0_us = DUMP_CLOCK0_US
+        proc.clock = lambda: DUMP_CLOCK0_US / 1e6
 
     def batch_time(i):
         return clock0_us + i * interval_us
@@ -349,11 +425,11 @@ def main():
         torch.cuda.synchronize(device)
     gen_s = time.perf_counter() - t_gen
 
-    # this box's own pinned H2D bandwidth, measured once before the timed region on a copy of the size one step
-    # ingests (best of 3): the record then says whether a step was bound by the link or by the code
+    # --full: this box's own pinned H2D bandwidth, measured once before the timed region on a copy of the size one
+    # step ingests (best of 3): the record then says whether a step was bound by the link or by the code
     # (pcie_fraction = ingest bytes per step / (h2d_gb_s * step time))
     h2d_gb_s = None
-    if on_gpu and comp_bytes:
+    if args.full and on_gpu and comp_bytes:
         kmax = max(range(len(comp_bytes)), key=comp_bytes.__getitem__)
         nb = comp_bytes[kmax]
         hsrc = pool[kmax] if isinstance(pool[kmax], torch.Tensor) else torch.empty(nb, dtype=torch.uint8,
@@ -539,6 +615,36 @@ def main():
         sizes.append(kafka_json[i % len(pool)] + 16 if source == "kafka" else rb.buf.shape[0])
         return m
 
+    dump_staged = []           # --dump-outputs: (output name, StagedOutput) of the last timed batch
+
+    def capture_outputs():
+        """--dump-outputs, before the last timed step: keep what that batch's outputs stage, and the lines each
+        payload renders to (a payload renders once; the dump reads the same lines the sinks were given)."""
+        def keep_render(p):
+            inner, box = p.render, []
+
+            def render(*a, **kw):
+                if not box:
+                    box.append(inner(*a, **kw))
+                return box[0]
+            p.render = render
+
+        def hook(op):
+            inner = op.stage
+
+            def stage(table, ctx=None):
+                st = inner(table, ctx)
+                for p in st.payloads():
+                    if hasattr(p, "render") and "render" not in vars(p):
+                        keep_render(p)
+                dump_staged.append((op.name, st))
+                return st
+            op.stage = stage
+        for op in proc.outputs:
+            hook(op)
+
+    if args.dump_outputs and args.steps < 1:
+        sys.exit("bench.py: --dump-outputs needs at least one timed step")
     from dxa.utils import settle_gc
     settle_gc()
     if args.switch_interval_ms is not None:
@@ -579,6 +685,8 @@ def main():
     t0 = time.perf_counter()
     last = None
     for i in range(warmup, warmup + args.steps):
+        if args.dump_outputs and i == warmup + args.steps - 1:
+            capture_outputs()
         step(i)
     last = proc.drain() or proc.last_metrics           # the last batch's outputs complete inside the timed region
     if on_gpu:
@@ -617,6 +725,15 @@ def main():
         check_framing(framing_checks)                      # after the timed region: one host sync
     if kdec is not None:
         kdec.check()                                       # every record batch decoded (one host sync)
+
+    dumped = None
+    if args.dump_outputs:
+        rendered = []
+        for name, st in dump_staged:
+            payloads = [p for p in dict((id(p), p) for p in st.payloads()).values() if not hasattr(p, "rows")]
+            for k, p in enumerate(payloads or [[]]):
+                rendered.append((name if k == 0 else f"{name}.{k}", p.render() if hasattr(p, "render") else p))
+        dumped = dump_outputs(args.dump_outputs, rendered, prefix=f"rank{rank}." if world > 1 else "")
 
     def pct(p, xs=None):
         xs = lat_sorted if xs is None else xs
@@ -691,6 +808,9 @@ def main():
         out["host_trace_ms"] = host_trace[-8:]           # (batch, stage() host ms, process_batch() host ms)
         out["host_sections_trace_ms"] = [(i, d) for i, _, d in host_sections_trace[-4:]]
         out["latency_trace_ms"] = [round(x * 1e3, 2) for x in lat]
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": len(dumped),
+                                 "rows": {k: v for k, v in dumped.items() if k.endswith(".rows.npy")}}
     if last:
         out["last_batch_outputs"] = {k: v for k, v in last.items() if k.startswith("Output_")}
     if flow == "join":
