@@ -18,8 +18,21 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over non-decimal numeric,
 boolean or timestamp arguments, with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
-exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary reports a hash collision, an over-long string key or a full
-dictionary — is answered by the paned path, which stays the reference implementation (tests compare both).
+exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
+reports a hash collision or an over-long string key — is answered by the paned path, which stays the reference
+implementation (tests compare both).
+
+**A full dictionary is rebuilt, not abandoned** (``DenseWindow.rebuild``).  The dictionary starts at ``DENSE_GROUPS``
+ids.  When the group counter passes the capacity, the panes accumulated since the last clean status are dropped from
+the ring (some of their rows went to the dump row), the groups that still have rows in the panes the ring holds are
+found on the device, renumbered densely — key columns into fresh tensors, every held pane slot, the hash table — and
+the dropped panes are accumulated again; when more than half the capacity is still live the capacity doubles, up to
+``DENSE_GROUPS_MAX``.  So a stream whose keys come and go stays on this path; only a window that really holds more
+than ``DENSE_GROUPS_MAX`` groups at once (or whose grown ring would not fit in memory) falls back for good.  A stream
+whose live set sits just under ``DENSE_GROUPS_MAX`` rebuilds as often as a few new keys arrive: accepted, and counted
+in ``DenseWindow.rebuilds``.  A rebuild is local to a rank and issues no collective: with N ranks a rank that
+rebuilds (or falls back) still hands ``dense_partials``' caller a partial table or None, and the caller's exchange is
+the same either way, so the ranks stay in step.
 """
 from __future__ import annotations
 
@@ -36,13 +49,19 @@ from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
 from .decimal import is_decimal
 
-DENSE_GROUPS = 1 << 16            # dictionary capacity per statement (groups ever seen); more → paned path
+DENSE_GROUPS = 1 << 16            # initial dictionary capacity per statement (groups with ids at one time)
+DENSE_GROUPS_MAX = 1 << 20        # the capacity grows to this at most (win_compact_kernel's single-workgroup scan)
 SCRATCH_SLOTS = 4                 # ring slots for panes only partly inside a window (re-aggregated every batch)
 BLOCK = 16                        # consecutive in-window panes pre-combined into one block slot, once
-N.register_sigs({"dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p]})
+N.register_sigs({"dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p]})
 _SUPPORTED = {"count", "sum", "min", "max", "avg", "mean"}
 
 N.register_sigs({
+    "dxa_win_live": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
+    "dxa_win_remap_dict": [N.c_p, N.c_p, N.c_p, N.c_i32, N.c_p],
+    "dxa_win_remap_ring": [N.c_p, N.c_p, N.c_i32, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_p, N.c_i32,
+                           N.c_p],
+    "dxa_win_rehash": [N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p],
     "dxa_win_sizes": [N.c_p],
     "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
     "dxa_win_combine": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
@@ -105,13 +124,40 @@ def _requests(aggs: Dict):
     return out
 
 
+def _target_capacity(live: int, gcap: int, gmax: int) -> int:
+    """The capacity a rebuild leaves the dictionary with: ``gcap``, doubled while more than half of it is live and
+    ``gmax`` allows.  After growth the dictionary is at most half full, so at least ``target / 2`` new keys arrive
+    before the next rebuild; at ``gmax`` a rebuild only recycles."""
+    target = gcap
+    while live > target // 2 and target < gmax:
+        target = min(2 * target, gmax)
+    return target
+
+
+def _table_slots(gcap: int) -> int:
+    """Hash-table slots for ``gcap`` groups: a power of two, at least twice the capacity."""
+    return 1 << max(10, (2 * gcap - 1).bit_length())
+
+
 class DenseWindow:
-    """Persistent state of one windowed statement (one fingerprint) on one device."""
+    """Persistent state of one windowed statement (one fingerprint) on one device.  ``gcap``: the dictionary's
+    current capacity; ``rebuilds``: how often it was rebuilt; ``disabled_reason``: None while the statement is
+    answered here, else why it went to the paned path for good."""
 
     def __init__(self, device, reqs, ring_slots: int):
         self.device = device
         self.reqs = reqs
         self.gcap = DENSE_GROUPS
+        self.gmax = max(DENSE_GROUPS_MAX, DENSE_GROUPS)
+        self.rebuilds = 0
+        self.disabled_reason: Optional[str] = None
+        # The three fields below belong to the one answer in flight: they assume that a deferred answer is completed
+        # (its ``finish`` run) before the next ``dense_answer`` for this fingerprint, which the processor guarantees
+        # (it completes every pending table at the end of the batch's statements).  A deferred answer that is
+        # dropped without being completed leaves ``dirty`` growing by one key per batch until the next clean status.
+        self.rebuild_pending = False    # the last status read "dictionary full" and nothing else
+        self.bad = 0                    # the last status' flags
+        self.dirty: List[int] = []      # keys of the panes accumulated since the last clean status
         self.R = ring_slots + SCRATCH_SLOTS
         self.NB = ring_slots // BLOCK + 4              # block slots after the pane and scratch slots
         self.blocks: Dict[int, tuple] = {}             # block id → (member entry ids, block slot, entries)
@@ -119,11 +165,15 @@ class DenseWindow:
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
         self.free = list(range(ring_slots))    # free pane slots (a heap: the lowest is taken first)
         self.disabled = False
-        self._pinned = [torch.empty(self.R, dtype=torch.int32, pin_memory=True) for _ in range(4)]
+        # pinned staging rows for slot lists (_dev_slots), used in rotation and never waited for: one pass over the
+        # window uploads at most one list per block slot (all of them right after a rebuild, which clears the block
+        # cache) and one for the answer, a rebuild one more, and every pass and every rebuild ends in a status read
+        # that drains the stream before the next begins — so NB + 2 rows are never rewritten while a copy is queued
+        self._pinned = torch.empty((self.NB + 2, self.R), dtype=torch.int32, pin_memory=True)
         self._scal_pin = [torch.empty(4, dtype=torch.int32, pin_memory=True) for _ in range(2)]
         self._scal_k = 0
         self._pin_k = 0
-        cap = 1 << max(10, (2 * self.gcap - 1).bit_length())
+        cap = _table_slots(self.gcap)
         self.hcap = cap
         dev = device
         self.htab = torch.empty(cap, dtype=torch.int64, device=dev)
@@ -134,27 +184,53 @@ class DenseWindow:
         self.ring = None
 
     # ---- layout -------------------------------------------------------------------------------------------------
-    def _build_layout(self, key_cols_in: List, args: Dict):
+    def _alloc_keys(self, kinds: List[tuple], gcap: int):
+        """Zero-filled dictionary key columns for ``gcap`` groups and the dump row → (keys, kernel descriptor)."""
         kw = _sizes()[2]
         dev = self.device
-        if not 1 <= len(key_cols_in) <= MAX_KEY_COLS:
-            raise Ineligible("key count")
         dc = _DictCols()
         keys = []
-        for j, k in enumerate(key_cols_in):
-            if isinstance(k, StrColumn):
-                vals = torch.zeros((self.gcap + 1) * kw, dtype=torch.uint8, device=dev)
-                lens = torch.zeros(self.gcap + 1, dtype=torch.int32, device=dev)
-                kind = 2
+        for j, (dtype, kind) in enumerate(kinds):
+            if kind == 2:
+                vals = torch.zeros((gcap + 1) * kw, dtype=torch.uint8, device=dev)
+                lens = torch.zeros(gcap + 1, dtype=torch.int32, device=dev)
             else:
-                vals = torch.zeros(self.gcap + 1, dtype=torch.int64, device=dev)
+                vals = torch.zeros(gcap + 1, dtype=torch.int64, device=dev)
                 lens = None
-                kind = 1 if k.data.dtype == torch.float64 else 0
-            valid = torch.zeros(self.gcap + 1, dtype=torch.uint8, device=dev)
-            keys.append((k.dtype, kind, vals, lens, valid))
+            valid = torch.zeros(gcap + 1, dtype=torch.uint8, device=dev)
+            keys.append((dtype, kind, vals, lens, valid))
             dc.c[j] = _DictCol(vals.data_ptr(), 0 if lens is None else lens.data_ptr(), valid.data_ptr(), kind, 0)
-        dc.ncols, dc.gcap = len(keys), self.gcap
-        self.keys, self.dictcols = keys, dc
+        dc.ncols, dc.gcap = len(keys), gcap
+        return keys, dc
+
+    def _alloc_ring(self, gcap: int):
+        """Ring, combined rows, keep flags and kept ids for ``gcap`` groups (the slot pitch is (gcap + 1) rows)."""
+        dev = self.device
+        rows = gcap + 1
+        ring = torch.empty((self.R + self.NB, rows * self.stride), dtype=torch.int64, device=dev)
+        acc = torch.zeros(rows * self.stride, dtype=torch.int64, device=dev)
+        keep = torch.empty(gcap, dtype=torch.uint8, device=dev)
+        out_idx = torch.empty(gcap, dtype=torch.int64, device=dev)
+        return ring, acc, keep, out_idx
+
+    def _bytes(self, gcap: int) -> int:
+        """Device bytes of the ring, key columns and table at capacity ``gcap`` (what a growing rebuild allocates)."""
+        kw = _sizes()[2]
+        rows = gcap + 1
+        total = (self.R + self.NB + 1) * rows * self.stride * 8 + 9 * gcap + 12 * _table_slots(gcap)
+        for _dt, kind, *_ in self.keys:
+            total += rows * ((kw + 4 if kind == 2 else 8) + 1)
+        return total
+
+    def _build_layout(self, key_cols_in: List, args: Dict):
+        if not 1 <= len(key_cols_in) <= MAX_KEY_COLS:
+            raise Ineligible("key count")
+        kinds = [(k.dtype, 2 if isinstance(k, StrColumn) else 1 if k.data.dtype == torch.float64 else 0)
+                 for k in key_cols_in]
+        try:
+            self.keys, self.dictcols = self._alloc_keys(kinds, self.gcap)
+        except torch.cuda.OutOfMemoryError:
+            raise Ineligible("memory") from None
         # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
         slots, keyed = [], {}
 
@@ -228,12 +304,80 @@ class DenseWindow:
         self.layout = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, plan=plan,
                            count_word=where[star], fin=fin, pfin=pfin, pspec_of=self._partial_spec)
         self.line_ops_t = torch.tensor(line_ops, dtype=torch.int32)
-        self.line_ops_dev = self.line_ops_t.to(dev)
-        rows = self.gcap + 1
-        self.ring = torch.empty((self.R + self.NB, rows * self.stride), dtype=torch.int64, device=dev)
-        self.acc = torch.zeros(rows * self.stride, dtype=torch.int64, device=dev)
-        self.keep = torch.empty(self.gcap, dtype=torch.uint8, device=dev)
-        self.out_idx = torch.empty(self.gcap, dtype=torch.int64, device=dev)
+        self.line_ops_dev = self.line_ops_t.to(self.device)
+        try:
+            self.ring, self.acc, self.keep, self.out_idx = self._alloc_ring(self.gcap)
+        except torch.cuda.OutOfMemoryError:
+            self.layout = None
+            raise Ineligible("memory") from None
+
+    # ---- a full dictionary: recycle the ids of groups that left the window, grow when most are still live ------
+    def release_expired(self, retained) -> None:
+        """Ring slots of panes the store no longer retains go back to the free heap."""
+        for k in [k for k in self.slot_of if k not in retained]:
+            heapq.heappush(self.free, self.slot_of.pop(k)[0])
+
+    def rebuild(self, retained, grow: bool) -> None:
+        """Renumber the dictionary over the groups that still have rows in held panes (module docstring); raises
+        ``Ineligible`` ("dictionary full" / "memory") when the statement has to leave the dense path.
+
+        ``grow``: an earlier rebuild in this call was not enough (re-accumulating the dropped panes overflowed
+        again), so the capacity has to double.  One host read (the live count).  Key columns always move into fresh
+        tensors: output strings of earlier batches are views of the old arena and may still be rendering.  Peak
+        extra memory: at an unchanged capacity only those key columns — each held pane slot is compacted through
+        one of the ring's own scratch slots (refilled every batch, so dead here); when the capacity grows the ring's
+        pitch changes, so a whole new ring, table and result buffers exist beside the old ones until the gather
+        has been queued (checked against half the free memory first).  Block slots are not remapped: the block
+        cache is cleared and complete blocks are combined again on next use."""
+        self.rebuild_pending = False
+        if grow and self.gcap >= self.gmax:
+            raise Ineligible("dictionary full")
+        # panes accumulated since the last clean status sent some rows to the dump row: the caller's pane loop
+        # accumulates them again after the rebuild
+        for k in self.dirty:
+            ent = self.slot_of.pop(k, None)
+            if ent is not None:
+                heapq.heappush(self.free, ent[0])
+        self.dirty = []
+        self.blocks.clear()
+        self.release_expired(retained)
+        L = self.layout
+        dev = self.device
+        st = N.stream_handle(dev)
+        slots = sorted(e[0] for e in self.slot_of.values())
+        N.call("dxa_win_live", N.ptr(self.ring), self.gcap, self.stride, N.ptr(self._dev_slots(slots)), len(slots),
+               N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+               N.ptr(self.out_idx), st)
+        live = int(self.scal[2])
+        target = _target_capacity(live, self.gcap, self.gmax)
+        if grow:
+            target = min(max(target, 2 * self.gcap), self.gmax)
+        grown = target != self.gcap
+        try:
+            if grown and self._bytes(target) > torch.cuda.mem_get_info(dev)[0] // 2:
+                raise Ineligible("memory")
+            keys, dc = self._alloc_keys([(k[0], k[1]) for k in self.keys], target)
+            ring, acc, keep, out_idx, htab, gid_of_slot, hcap = (self.ring, self.acc, self.keep, self.out_idx,
+                                                                 self.htab, self.gid_of_slot, self.hcap)
+            if grown:
+                ring, acc, keep, out_idx = self._alloc_ring(target)
+                hcap = _table_slots(target)
+                htab = torch.empty(hcap, dtype=torch.int64, device=dev)
+                gid_of_slot = torch.empty(hcap, dtype=torch.int32, device=dev)
+        except torch.cuda.OutOfMemoryError:
+            raise Ineligible("memory") from None
+        N.call("dxa_win_remap_dict", ctypes.addressof(self.dictcols), ctypes.addressof(dc), N.ptr(self.out_idx), live,
+               st)
+        host_slots = (ctypes.c_int32 * max(1, len(slots)))(*slots)
+        N.call("dxa_win_remap_ring", N.ptr(self.ring), N.ptr(ring), self.gcap, target, self.stride,
+               ctypes.addressof(host_slots), len(slots), self.R - 1, N.ptr(self.line_ops_dev), N.ptr(self.out_idx),
+               live, st)
+        N.call("dxa_win_rehash", ctypes.addressof(dc), N.ptr(htab), N.ptr(gid_of_slot), hcap, live, N.ptr(self.scal),
+               st)
+        self.keys, self.dictcols, self.gcap = keys, dc, target
+        self.ring, self.acc, self.keep, self.out_idx = ring, acc, keep, out_idx
+        self.htab, self.gid_of_slot, self.hcap = htab, gid_of_slot, hcap
+        self.rebuilds += 1
 
     # ---- one pane into one ring slot ----------------------------------------------------------------------------
     def accumulate(self, table, slot_idx: int, alias, where, gexprs, ctx):
@@ -316,7 +460,7 @@ class DenseWindow:
 
     def _dev_slots(self, slots: List[int]) -> torch.Tensor:
         pin = self._pinned[self._pin_k]
-        self._pin_k = (self._pin_k + 1) % len(self._pinned)
+        self._pin_k = (self._pin_k + 1) % self._pinned.shape[0]
         pin[:len(slots)] = torch.tensor(slots, dtype=torch.int32)
         return pin[:len(slots)].to(self.device, non_blocking=True)
 
@@ -336,13 +480,14 @@ class DenseWindow:
         dst = free[0]
         member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
         N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(self._dev_slots(member_slots)),
-               len(member_slots), N.ptr(self.line_ops_dev), dst, N.stream_handle(self.device))
+               len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.stream_handle(self.device))
         self.blocks[bid] = (members, dst, list(mem))
         return dst
 
     # ---- the window's answer --------------------------------------------------------------------------------------
     def answer(self, slots: List[int], partial_proto=None, defer: bool = False):
-        """Combine ``slots`` → (key columns, {agg key → column}, groups) or None (fall back: collision / full).
+        """Combine ``slots`` → (key columns, {agg key → column}, groups), or None: a collision or an over-long key
+        (the caller falls back for good) or a full dictionary (the caller rebuilds it and asks again).
         With ``partial_proto`` (an empty partial table of ``distagg.local_partials``' layout, and its plan) the
         result is instead this rank's window as a partial table of exactly that layout, for the key exchange.
         ``defer``: return a function that completes the answer later — the kernels are queued and the status is on
@@ -373,8 +518,13 @@ class DenseWindow:
     def _finish(self, status, bufs, fin, partial_proto):
         L = self.layout
         ng_all, bad, nout, _ = status
+        self.bad = bad
         if bad:
+            # a full dictionary and nothing else: rebuilt before the next answer (dense_answer); a collision or an
+            # over-long key (never cleared on the device) sends the statement to the paned path for good
+            self.rebuild_pending = bad == 2
             return None
+        self.dirty = []
         okey, olen, ovalid, dst, dvalid = bufs
         out_keys = []
         for j, (dt, kind, vals, lens, valid) in enumerate(self.keys):
@@ -490,7 +640,10 @@ def dense_partials(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, empty):
 
 def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_proto=None, defer: bool = False):
     """The window statement's (key columns, finals, groups, group exprs) from the dense ring, or None.
-    ``defer``: instead a function returning that tuple (or None: fall back) once the status read completes."""
+    ``defer``: instead a function returning that tuple (or None: fall back) once the status read completes.
+    None leaves the statement to the paned path: for good when the state is disabled (``disabled_reason``), for
+    this one call when a deferred status reads "dictionary full" — the caller's re-run comes back here, rebuilds
+    the dictionary and answers from the ring."""
     from .. import parallel as P
     from .query import _resolve_group_expr
     from .expr import Scope
@@ -512,73 +665,37 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
             state = states[fp] = DenseWindow(dev, _requests(aggs), max(panes, len(pieces) + 2))
         proto = pieces[0][0].table
         gexprs = [_resolve_group_expr(g, Scope.of_table(proto, alias), items) for g in sel.group_by]
-        # ring slots: a pane keeps its slot while the store retains it (a pane's rows never change — its table is only
-        # compacted once; the pane object guards a re-created pane), an expired pane's slot goes back to the free
-        # heap.  One pass over the window's panes.
-        slot_of = state.slot_of
-        past = store.past
-        for k in [k for k in slot_of if k not in past]:
-            heapq.heappush(state.free, slot_of.pop(k)[0])
-        scratch = list(range(state.R - SCRATCH_SLOTS, state.R))
-        slots = []
-        span = BLOCK * max(1, store.interval_us)
-        by_block: Dict[int, list] = {}
-        for pane, full in pieces:
-            if full:                                   # (pieces' "full" includes every row having a timestamp)
-                ent = slot_of.get(pane.key)
-                if ent is None or ent[1] is not pane:
-                    if ent is not None:
-                        heapq.heappush(state.free, ent[0])
-                        del slot_of[pane.key]
-                    if not state.free:
-                        raise Ineligible("ring full")
-                    sl = heapq.heappop(state.free)
-                    state.accumulate(pane.table, sl, alias, sel.where, gexprs, ctx)
-                    ent = slot_of[pane.key] = (sl, pane, pane.key // span, pane.key)
-                mem = by_block.get(ent[2])
-                if mem is None:
-                    by_block[ent[2]] = [ent]
-                else:
-                    mem.append(ent)
-            else:
-                # a pane only partly inside the window: its in-range rows, re-aggregated into a scratch slot
-                if not scratch:
-                    raise Ineligible("too many clipped panes")
-                sl = scratch.pop(0)
-                state.accumulate(t.clipped(pane), sl, alias, sel.where, gexprs, ctx)
-                slots.append(sl)
-        # complete blocks of BLOCK consecutive panes: one pre-combined slot each (the per-batch combine then reads
-        # ~20 block slots and the loose panes at the window's edges instead of 300 pane slots)
-        for bid in [b for b in state.blocks if b not in by_block]:
-            del state.blocks[bid]
-        for bid, mem in by_block.items():
-            if len(mem) == BLOCK:
-                slots.append(state.block_slot(bid, mem))
-            else:
-                state.blocks.pop(bid, None)
-                slots.extend(e[0] for e in mem)
-        got = state.answer(slots, partial_proto, defer=defer and partial_proto is None)
-    except Ineligible:
+        # A status that reads "dictionary full" (in this call, or in the deferred completion of the last one) is
+        # answered by a rebuild and another pass over the window's panes, which accumulates the dropped panes
+        # again.  Every rebuild after the first in one call doubles the capacity or gives up, so the loop ends
+        # within log2(DENSE_GROUPS_MAX / DENSE_GROUPS) + 2 passes.
+        rebuilt = False
+        while True:
+            if state.rebuild_pending:
+                state.rebuild(store.past, grow=rebuilt)
+                rebuilt = True
+            got = _enqueue(state, t, pieces, sel, alias, gexprs, ctx, partial_proto, defer)
+            if got is not None or not state.rebuild_pending:
+                break
+    except Ineligible as why:
         state = states.get(fp)
         if state is not None:
-            state.disabled = True
-            state.ring = state.acc = None
+            _disable(state, str(why))
         else:
-            states[fp] = _Disabled()
+            states[fp] = _Disabled(str(why))
         return None
     if callable(got):
         def finish():
             res = got()
             if res is None:
-                state.disabled = True
-                state.ring = state.acc = None
+                if not state.rebuild_pending:   # else: the caller's re-run of the statement rebuilds and answers
+                    _disable(state, _flag_reason(state.bad))
                 return None
             out_keys, finals, ng = res
             return out_keys, finals, ng, gexprs
         return finish
     if got is None:
-        state.disabled = True
-        state.ring = state.acc = None
+        _disable(state, _flag_reason(state.bad))
         return None
     if partial_proto is not None:
         return got, gexprs
@@ -586,5 +703,69 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
     return out_keys, finals, ng, gexprs
 
 
+def _flag_reason(bad: int) -> str:
+    return "hash collision" if bad & 1 else "key too long" if bad & 4 else "dictionary full"
+
+
+def _disable(state, reason: str) -> None:
+    state.disabled = True
+    state.disabled_reason = reason
+    state.ring = state.acc = None
+
+
+def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defer: bool):
+    """One pass over the window's panes: new panes into ring slots, complete blocks combined, the answer queued →
+    ``DenseWindow.answer``'s result."""
+    store = t.store
+    # ring slots: a pane keeps its slot while the store retains it (a pane's rows never change — its table is only
+    # compacted once; the pane object guards a re-created pane), an expired pane's slot goes back to the free
+    # heap.  One pass over the window's panes.
+    slot_of = state.slot_of
+    state.release_expired(store.past)
+    scratch = list(range(state.R - SCRATCH_SLOTS, state.R))
+    slots = []
+    span = BLOCK * max(1, store.interval_us)
+    by_block: Dict[int, list] = {}
+    for pane, full in pieces:
+        if full:                                   # (pieces' "full" includes every row having a timestamp)
+            ent = slot_of.get(pane.key)
+            if ent is None or ent[1] is not pane:
+                if ent is not None:
+                    heapq.heappush(state.free, ent[0])
+                    del slot_of[pane.key]
+                if not state.free:
+                    raise Ineligible("ring full")
+                sl = heapq.heappop(state.free)
+                state.accumulate(pane.table, sl, alias, sel.where, gexprs, ctx)
+                ent = slot_of[pane.key] = (sl, pane, pane.key // span, pane.key)
+                state.dirty.append(pane.key)
+            mem = by_block.get(ent[2])
+            if mem is None:
+                by_block[ent[2]] = [ent]
+            else:
+                mem.append(ent)
+        else:
+            # a pane only partly inside the window: its in-range rows, re-aggregated into a scratch slot
+            if not scratch:
+                raise Ineligible("too many clipped panes")
+            sl = scratch.pop(0)
+            state.accumulate(t.clipped(pane), sl, alias, sel.where, gexprs, ctx)
+            slots.append(sl)
+    # complete blocks of BLOCK consecutive panes: one pre-combined slot each (the per-batch combine then reads
+    # ~20 block slots and the loose panes at the window's edges instead of 300 pane slots)
+    for bid in [b for b in state.blocks if b not in by_block]:
+        del state.blocks[bid]
+    for bid, mem in by_block.items():
+        if len(mem) == BLOCK:
+            slots.append(state.block_slot(bid, mem))
+        else:
+            state.blocks.pop(bid, None)
+            slots.extend(e[0] for e in mem)
+    return state.answer(slots, partial_proto, defer=defer and partial_proto is None)
+
+
 class _Disabled:
     disabled = True
+
+    def __init__(self, reason: str):
+        self.disabled_reason = reason

@@ -18,6 +18,10 @@
 //                    and listed in group order;
 //   5. win_emit    — every kept group's key columns and finished aggregates are written by output position, so the
 //                    host only slices the outputs after its read.
+// When the dictionary fills (the group counter passes the capacity) it is rebuilt instead of abandoned: win_live
+// finds the groups that still have rows in the panes the ring holds, win_remap_dict / win_remap_slot renumber them
+// densely in the key columns and in every held pane slot, win_rehash refills the cleared table (dxa_win_live …
+// dxa_win_rehash below; the policy is the host's, dxa/engine/window_dense.py DenseWindow.rebuild).
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -69,20 +73,27 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
   return k.kind == KC_F64 ? norm_f64_bits(((const double*)k.data)[i]) : (uint64_t)((const int64_t*)k.data)[i];
 }
 
-// 5. combine the window's ring slots: out[g][w] = ⊕ over slots s of ring[s][g][w], for g < groups in the dictionary
+// 5. combine the window's ring slots: out[g][w] = ⊕ over slots s of ring[s][g][w], for g < groups in the dictionary.
+// With ``fixed_rows`` (a block combine) every one of those rows is written, but the member slots are read only for
+// the groups the dictionary holds: the rows above them are the identity in every member (no row has been
+// accumulated there), so they are written as the identity without a read and the cost follows the groups in use,
+// not the capacity.  (A template parameter, so the per-batch combine keeps its wave-uniform slot loop.)
+template <bool kBlock>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
-                                                          int32_t nslots, int32_t stride,
+                                                          int32_t nslots_in, int32_t stride,
                                                           const int32_t* __restrict__ line_op,
                                                           const int32_t* __restrict__ scal, int32_t gcap,
                                                           int32_t fixed_rows, unsigned long long* __restrict__ out) {
-  int32_t ng = fixed_rows > 0 ? fixed_rows : scal[0];
-  if (fixed_rows <= 0 && ng > gcap) ng = gcap;
-  const int64_t total = (int64_t)ng * stride;
+  int32_t ng = scal[0];
+  if (ng > gcap) ng = gcap;
+  const int64_t held = (int64_t)ng * stride;
+  const int64_t total = kBlock ? (int64_t)fixed_rows * stride : held;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int w = (int)(idx % stride);
     const int op = line_op[w >> 3];
+    const int nslots = (!kBlock || idx < held) ? nslots_in : 0;   // no member reads above the groups in use
     if (op == MA_ADD_F64) {
       double acc = 0.0;
       for (int s = 0; s < nslots; ++s) acc += __longlong_as_double((long long)ring[(int64_t)slots[s] * slot_words + idx]);
@@ -327,6 +338,96 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
   }
 }
 
+// ---- dictionary rebuild (see dxa_win_live below): old group out_idx[p] becomes group p, p < live -----------------
+
+// key columns: one thread per live group copies its entry of every column (a string slot is kKeyWidth / 8 words)
+__global__ __launch_bounds__(256) void win_remap_dict_kernel(const DictCols src, const DictCols dst,
+                                                             const int64_t* __restrict__ out_idx, int32_t live) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < live; p += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t g = out_idx[p];
+    for (int j = 0; j < src.ncols; ++j) {
+      const DictCol& a = src.c[j];
+      const DictCol& b = dst.c[j];
+      b.valid[p] = a.valid[g];
+      if (a.kind == KC_STR) {
+        const uint64_t* x = (const uint64_t*)((const uint8_t*)a.vals + g * kKeyWidth);
+        uint64_t* y = (uint64_t*)((uint8_t*)b.vals + p * kKeyWidth);
+        for (int q = 0; q < kKeyWidth / 8; ++q) y[q] = x[q];
+        b.lens[p] = a.lens[g];
+      } else {
+        ((int64_t*)b.vals)[p] = ((const int64_t*)a.vals)[g];
+      }
+    }
+  }
+}
+
+// one ring slot: dst row p = src row out_idx[p] for p < live, the accumulator identity (agg_multi_init_kernel's)
+// for every other row up to and including the dump row — a group that draws one of those ids later has no rows in
+// this pane.  ``src`` and ``dst`` are different slots; consecutive lanes move consecutive words of a row.
+__global__ __launch_bounds__(256) void win_remap_slot_kernel(const unsigned long long* __restrict__ src,
+                                                             unsigned long long* __restrict__ dst,
+                                                             const int64_t* __restrict__ out_idx, int32_t live,
+                                                             int32_t rows, int32_t stride,
+                                                             const int32_t* __restrict__ line_op) {
+  const int64_t total = (int64_t)rows * stride;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = idx / stride;
+    const int w = (int)(idx - p * stride);
+    unsigned long long v = line_op[w >> 3] == MA_MAX_I64 ? 0x8000000000000000ull : 0ull;
+    if (p < live) v = src[out_idx[p] * stride + w];
+    dst[idx] = v;
+  }
+}
+
+// a dictionary entry's key hash: equal to row_hash of the row that claimed it (the entry holds the row's key words
+// — doubles already normalised — or its string bytes).  Recomputed here rather than kept per group at insert: the
+// insert kernel is the hot one, and a [gcap + 1] hash array written by every claiming lane would cost it a store
+// per new key and the ring 8 bytes per group for a value a rare rebuild can derive.
+__device__ __forceinline__ uint64_t dict_hash(const DictCols& d, int64_t g) {
+  uint64_t h = 0;
+  for (int j = 0; j < d.ncols; ++j) {
+    const DictCol& c = d.c[j];
+    uint64_t x;
+    if (!c.valid[g]) x = dxa::kNullHash;
+    else if (c.kind == KC_STR) x = dxa::hash_bytes((const uint8_t*)c.vals + g * kKeyWidth, c.lens[g]);
+    else x = dxa::hash_i64((uint64_t)((const int64_t*)c.vals)[g]);
+    h = j ? dxa::hash_combine(h, x) : x;
+  }
+  return h;
+}
+
+// the table of the renumbered dictionary (cleared before): one thread per live group claims the first empty slot
+// along its probe sequence and stores the id.  Live keys have distinct hashes (a duplicate raised the collision
+// flag at insert), so nobody looks an entry up here and nothing waits: a lost CAS moves on to the next slot.
+// Thread 0 publishes the new group count and clears the "dictionary full" flag (atomically: another lane may be
+// raising the collision flag, which is never cleared).
+__global__ __launch_bounds__(256) void win_rehash_kernel(const DictCols d, uint64_t* __restrict__ keys,
+                                                         int64_t cap_mask, int32_t* __restrict__ gid_of_slot,
+                                                         int32_t live, int32_t* __restrict__ scal) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    scal[0] = live;
+    atomicAnd(&scal[1], ~2);
+  }
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < live; g += (int64_t)gridDim.x * blockDim.x) {
+    const uint64_t k = dxa::fix_key(dict_hash(d, g));
+    int64_t s = (int64_t)(dxa::fmix64(k) & (uint64_t)cap_mask);
+    bool placed = false;
+    for (int64_t probes = 0; probes <= cap_mask && !placed; ++probes) {
+      const uint64_t prev = atomicCAS((unsigned long long*)&keys[s], (unsigned long long)dxa::kEmpty,
+                                      (unsigned long long)k);
+      if (prev == dxa::kEmpty) {
+        gid_of_slot[s] = (int32_t)g;
+        placed = true;
+      } else if (prev == k) {
+        break;                                             // two live groups with one hash: reported below
+      }
+      s = (s + 1) & cap_mask;
+    }
+    if (!placed) atomicOr(&scal[1], 1);
+  }
+}
+
 }  // namespace
 
 DXA_API int dxa_win_sizes(int32_t* out) {
@@ -352,8 +453,8 @@ DXA_API int dxa_win_combine(const void* ring, int32_t gcap, int32_t stride, cons
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL(win_combine_kernel, dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0, s,
-                     (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
+  hipLaunchKernelGGL(win_combine_kernel<false>, dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+                     s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
                      (unsigned long long*)acc);
   hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
                      (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
@@ -361,16 +462,79 @@ DXA_API int dxa_win_combine(const void* ring, int32_t gcap, int32_t stride, cons
   return (int)hipGetLastError();
 }
 
-// a block of ring slots pre-combined into another ring slot (every row, so groups the dictionary gains later read
-// the identity there): out = ring slot ``dst``
+// a block of ring slots pre-combined into another ring slot (every row is written, so groups the dictionary gains
+// later read the identity there; the members are read only for the scal[0] groups in use): out = ring slot ``dst``
 DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                                  const int32_t* line_op, int32_t dst, void* st) {
+                                  const int32_t* line_op, int32_t dst, const int32_t* scal, void* st) {
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL(win_combine_kernel, dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)), dim3(256), 0,
-                     s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, (const int32_t*)nullptr,
+  hipLaunchKernelGGL(win_combine_kernel<true>, dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
+                     dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
                      gcap, gcap + 1, r + (int64_t)dst * slot_words);
+  return (int)hipGetLastError();
+}
+
+// ---- dictionary rebuild: when the group counter passes the capacity the host drops the panes accumulated since the
+// last clean status, finds the groups that still have rows in the panes it holds (dxa_win_live), and renumbers them
+// densely: old id out_idx[p] becomes p, p < live.  Off the hot path (once per ~capacity / 2 new keys at the least).
+
+// The live groups of the given pane slots: the window combine, keep and compact passes over those slots →
+// out_idx[0 .. scal[2]) = the old ids with COUNT(*) > 0 there, increasing.
+DXA_API int dxa_win_live(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                         const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
+                         int64_t* out_idx, void* st) {
+  return dxa_win_combine(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, st);
+}
+
+// The dictionary's key columns into fresh ones (``dst`` is zero-filled; earlier batches' output strings are views of
+// the old arena and may still be rendering, so nothing moves in place).
+DXA_API int dxa_win_remap_dict(const void* src, const void* dst, const int64_t* out_idx, int32_t live, void* st) {
+  const DictCols& a = *(const DictCols*)src;
+  const DictCols& b = *(const DictCols*)dst;
+  if (live < 0 || live > a.gcap || live > b.gcap || a.ncols != b.ncols) return (int)hipErrorInvalidValue;
+  if (live == 0) return 0;
+  hipLaunchKernelGGL(win_remap_dict_kernel, dim3(dxa_blocks(live, 256)), dim3(256), 0, (hipStream_t)st, a, b, out_idx,
+                     live);
+  return (int)hipGetLastError();
+}
+
+// The pane slots ``slots`` (a HOST array) of ``src`` [.][(gcap_src + 1) * stride] into the same slots of ``dst``
+// [.][(gcap_dst + 1) * stride].  A grown ring is a new allocation and each slot is gathered straight into it.  With
+// src == dst (capacity unchanged) each slot is gathered into ``tmp_slot`` — a slot of the ring whose contents are
+// dead during a rebuild (the host passes a scratch slot: those are refilled every batch) — and copied back, so the
+// in-place form needs no extra memory and has no cross-thread hazard.
+DXA_API int dxa_win_remap_ring(const void* src, void* dst, int32_t gcap_src, int32_t gcap_dst, int32_t stride,
+                               const int32_t* slots, int32_t nslots, int32_t tmp_slot, const int32_t* line_op,
+                               const int64_t* out_idx, int32_t live, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  const bool in_place = src == dst;
+  if (live < 0 || live > gcap_src || live > gcap_dst || (in_place && gcap_src != gcap_dst))
+    return (int)hipErrorInvalidValue;
+  const int64_t src_words = (int64_t)(gcap_src + 1) * stride, dst_words = (int64_t)(gcap_dst + 1) * stride;
+  const unsigned long long* from = (const unsigned long long*)src;
+  unsigned long long* to = (unsigned long long*)dst;
+  for (int32_t k = 0; k < nslots; ++k) {
+    if (in_place && slots[k] == tmp_slot) return (int)hipErrorInvalidValue;
+    unsigned long long* out = to + (int64_t)(in_place ? tmp_slot : slots[k]) * dst_words;
+    hipLaunchKernelGGL(win_remap_slot_kernel, dim3(dxa_blocks(dst_words, 256, 256 * 64)), dim3(256), 0, s,
+                       from + (int64_t)slots[k] * src_words, out, out_idx, live, gcap_dst + 1, stride, line_op);
+    if (in_place) hipMemcpyAsync(to + (int64_t)slots[k] * dst_words, out, (size_t)dst_words * 8,
+                                 hipMemcpyDeviceToDevice, s);
+  }
+  return (int)hipGetLastError();
+}
+
+// The hash table of the renumbered dictionary: cleared as dxa_win_init clears it, then every live group's hash goes
+// back in; the same launch sets the group counter to ``live`` and clears the "dictionary full" flag.
+DXA_API int dxa_win_rehash(const void* dictcols, uint64_t* keys, int32_t* gid_of_slot, int64_t cap, int32_t live,
+                           int32_t* scal, void* st) {
+  const DictCols& d = *(const DictCols*)dictcols;
+  if (live < 0 || live > d.gcap || cap < 2 * (int64_t)d.gcap || (cap & (cap - 1))) return (int)hipErrorInvalidValue;
+  const int rc = dxa_win_init(keys, gid_of_slot, cap, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(win_rehash_kernel, dim3(dxa_blocks(live, 256)), dim3(256), 0, (hipStream_t)st, d, keys, cap - 1,
+                     gid_of_slot, live, scal);
   return (int)hipGetLastError();
 }
 
