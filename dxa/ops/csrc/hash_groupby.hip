@@ -31,6 +31,14 @@ __global__ void hash_i64_kernel(const int64_t* __restrict__ v, const uint8_t* __
   }
 }
 
+// A double key's word: -0.0 groups with 0.0 and every NaN is one key.  The hashes and the verify kernels both read
+// keys through this, so rows that hash alike for either reason also compare alike.
+__device__ __forceinline__ uint64_t norm_f64_bits(double d) {
+  if (d == 0.0) d = 0.0;                                   // -0.0 → 0.0
+  const uint64_t b = (uint64_t)__double_as_longlong(d);
+  return d != d ? 0x7ff8000000000000ull : b;               // canonical NaN
+}
+
 __global__ void hash_f64_kernel(const double* __restrict__ v, const uint8_t* __restrict__ valid, int64_t n,
                                 uint64_t* __restrict__ out, int combine) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -38,11 +46,7 @@ __global__ void hash_f64_kernel(const double* __restrict__ v, const uint8_t* __r
     if (valid && !valid[i]) {
       h = dxa::kNullHash;
     } else {
-      double d = v[i];
-      if (d == 0.0) d = 0.0;                       // -0.0 → 0.0
-      uint64_t bits = (uint64_t)__double_as_longlong(d);
-      if (d != d) bits = 0x7ff8000000000000ull;   // canonical NaN
-      h = dxa::hash_i64(bits);
+      h = dxa::hash_i64(norm_f64_bits(v[i]));
     }
     out[i] = combine ? dxa::hash_combine(out[i], h) : h;
   }
@@ -81,13 +85,7 @@ struct KeyCols {
 __device__ __forceinline__ uint64_t key_hash(const KeyCol& k, int64_t i) {
   if (k.valid && !k.valid[i]) return dxa::kNullHash;
   if (k.kind == KC_STR) return dxa::hash_bytes((const uint8_t*)k.data + k.starts[i], k.lens[i]);
-  if (k.kind == KC_F64) {
-    double d = ((const double*)k.data)[i];
-    if (d == 0.0) d = 0.0;
-    uint64_t bits = (uint64_t)__double_as_longlong(d);
-    if (d != d) bits = 0x7ff8000000000000ull;
-    return dxa::hash_i64(bits);
-  }
+  if (k.kind == KC_F64) return dxa::hash_i64(norm_f64_bits(((const double*)k.data)[i]));
   return dxa::hash_i64((uint64_t)((const int64_t*)k.data)[i]);
 }
 
@@ -121,6 +119,8 @@ __global__ void verify_multi_kernel(const KeyCols a, const int32_t* __restrict__
           const int32_t av = l - q < 8 ? l - q : 8;
           diff = load_part(x + q, av) != load_part(y + q, av);
         }
+      } else if (k.kind == KC_F64) {
+        diff = norm_f64_bits(((const double*)k.data)[i]) != norm_f64_bits(((const double*)k.data)[r]);
       } else {
         diff = ((const int64_t*)k.data)[i] != ((const int64_t*)k.data)[r];     // bit equality (as verify_i64)
       }
@@ -235,7 +235,9 @@ __global__ void group_gather_kernel(const int32_t* __restrict__ slot_of_row, con
   }
 }
 
-// Exact-key verification: flag rows whose key columns differ from their group representative's.
+// Exact-key verification: flag rows whose key columns differ from their group representative's.  Doubles (kF64)
+// compare the normalised words that hash_f64_kernel hashes; everything else compares bits.
+template <bool kF64>
 __global__ void verify_i64_kernel(const int64_t* __restrict__ v, const uint8_t* __restrict__ valid,
                                   const int32_t* __restrict__ gid, const int32_t* __restrict__ rep, int64_t n,
                                   int32_t* __restrict__ bad) {
@@ -243,7 +245,14 @@ __global__ void verify_i64_kernel(const int64_t* __restrict__ v, const uint8_t* 
     const int32_t r = rep[gid[i]];
     const bool vi = valid ? valid[i] != 0 : true;
     const bool vr = valid ? valid[r] != 0 : true;
-    if (vi != vr || (vi && v[i] != v[r])) atomicAdd(bad, 1);
+    bool diff = vi != vr;
+    if (!diff && vi) {
+      if constexpr (kF64)
+        diff = norm_f64_bits(__longlong_as_double(v[i])) != norm_f64_bits(__longlong_as_double(v[r]));
+      else
+        diff = v[i] != v[r];
+    }
+    if (diff) atomicAdd(bad, 1);
   }
 }
 
@@ -289,22 +298,37 @@ __global__ void verify_str_kernel(const uint8_t* __restrict__ arena, const int64
 enum : int32_t { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_COUNT = 3 };
 enum : int32_t { VT_I64 = 0, VT_F64 = 1 };
 
+// total order of doubles as signed 64-bit integers (NaN canonical and greatest, as Spark orders it)
+__device__ __forceinline__ long long f64_ordered(double d) {
+  long long b = __double_as_longlong(d);
+  if (d != d) b = 0x7ff8000000000000ll;
+  return b >= 0 ? b : (b ^ 0x7fffffffffffffffll);
+}
+__device__ __forceinline__ unsigned long long f64_from_ordered(long long k) {
+  return (unsigned long long)(k >= 0 ? k : (k ^ 0x7fffffffffffffffll));
+}
+
+// MIN / MAX of doubles (LDS or global accumulators, held as doubles): compared in f64_ordered's total order, so
+// -0.0 < 0.0, NaN is the greatest value and the answer does not depend on which row's atomic lands last (`<=` on
+// the doubles themselves is false for NaN on either side).  A NaN is stored as the canonical one.
 __device__ __forceinline__ void lds_f64_min(double* p, double v) {
   unsigned long long* a = (unsigned long long*)p;
+  const long long kv = f64_ordered(v);
   unsigned long long old = *a, assumed;
   do {
     assumed = old;
-    if (__longlong_as_double((long long)assumed) <= v) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+    if (f64_ordered(__longlong_as_double((long long)assumed)) <= kv) return;
+    old = atomicCAS(a, assumed, f64_from_ordered(kv));
   } while (old != assumed);
 }
 __device__ __forceinline__ void lds_f64_max(double* p, double v) {
   unsigned long long* a = (unsigned long long*)p;
+  const long long kv = f64_ordered(v);
   unsigned long long old = *a, assumed;
   do {
     assumed = old;
-    if (__longlong_as_double((long long)assumed) >= v) return;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
+    if (f64_ordered(__longlong_as_double((long long)assumed)) >= kv) return;
+    old = atomicCAS(a, assumed, f64_from_ordered(kv));
   } while (old != assumed);
 }
 
@@ -331,7 +355,8 @@ template <int VT, int OP>
 __device__ __forceinline__ uint64_t identity_bits() {
   if constexpr (OP == AGG_SUM || OP == AGG_COUNT) return 0ull;
   if constexpr (VT == VT_I64) return OP == AGG_MIN ? 0x7fffffffffffffffull : 0x8000000000000000ull;
-  return OP == AGG_MIN ? 0x7ff0000000000000ull /* +inf */ : 0xfff0000000000000ull /* -inf */;
+  // the greatest and the least double of f64_ordered's order
+  return OP == AGG_MIN ? 0x7ff8000000000000ull /* NaN */ : 0xfff0000000000000ull /* -inf */;
 }
 
 // LDS-privatised aggregation: one accumulator array of ngroups per workgroup.
@@ -428,13 +453,6 @@ struct MultiAggArgs {
   unsigned long long* out;
   MultiAggSlot slot[kMaxAggSlots];
 };
-
-// total order of doubles as signed 64-bit integers (NaN canonical and greatest, as Spark orders it)
-__device__ __forceinline__ long long f64_ordered(double d) {
-  long long b = __double_as_longlong(d);
-  if (d != d) b = 0x7ff8000000000000ll;
-  return b >= 0 ? b : (b ^ 0x7fffffffffffffffll);
-}
 
 __global__ __launch_bounds__(256) void agg_multi_init_kernel(MultiAggArgs a, int32_t ngroups) {
   const int64_t total = (int64_t)ngroups * a.nlines * 8;
@@ -626,8 +644,17 @@ DXA_API int dxa_group_build(const uint64_t* h, int64_t n, uint64_t* keys, int64_
 DXA_API int dxa_verify_i64(const int64_t* v, const uint8_t* valid, const int32_t* gid, const int32_t* rep, int64_t n,
                            int32_t* bad, void* st) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(verify_i64_kernel, dim3(dxa_blocks(n, 256)), dim3(256), 0, (hipStream_t)st, v, valid, gid, rep,
-                     n, bad);
+  hipLaunchKernelGGL(verify_i64_kernel<false>, dim3(dxa_blocks(n, 256)), dim3(256), 0, (hipStream_t)st, v, valid, gid,
+                     rep, n, bad);
+  return (int)hipGetLastError();
+}
+
+// a double key column (its bits as int64): -0.0 equals 0.0 and every NaN equals every NaN, as dxa_hash_f64 hashes them
+DXA_API int dxa_verify_f64(const int64_t* v, const uint8_t* valid, const int32_t* gid, const int32_t* rep, int64_t n,
+                           int32_t* bad, void* st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(verify_i64_kernel<true>, dim3(dxa_blocks(n, 256)), dim3(256), 0, (hipStream_t)st, v, valid, gid,
+                     rep, n, bad);
   return (int)hipGetLastError();
 }
 

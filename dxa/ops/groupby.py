@@ -82,9 +82,12 @@ def group_rows(keys: List, ordered: bool = True) -> Groups:
                        N.ptr(gid), N.ptr(rep), n, bad_ptr, st)
             else:
                 d = k.data
-                if d.dtype != torch.int64:
-                    d = d.view(torch.int64) if d.dtype == torch.float64 else d.to(torch.int64)
-                N.call("dxa_verify_i64", N.ptr(d), N.ptr(N.u8(k.valid)), N.ptr(gid), N.ptr(rep), n, bad_ptr, st)
+                fn = "dxa_verify_i64"
+                if d.dtype == torch.float64:       # compared as the hash sees them: -0.0 is 0.0, every NaN is one
+                    d, fn = d.view(torch.int64), "dxa_verify_f64"
+                elif d.dtype != torch.int64:
+                    d = d.to(torch.int64)
+                N.call(fn, N.ptr(d), N.ptr(N.u8(k.valid)), N.ptr(gid), N.ptr(rep), n, bad_ptr, st)
         ng, bad = scal.tolist()
         if bad:
             return _exact_groups(keys, device)
@@ -113,7 +116,7 @@ def group_rows(keys: List, ordered: bool = True) -> Groups:
     rep = rep[order]
     # verify exact equality against representatives
     for k in keys:
-        vals = k.to_pylist()
+        vals = _key_values(k)
         rp = rep.tolist()
         g = gid.tolist()
         for i in range(n):
@@ -122,8 +125,20 @@ def group_rows(keys: List, ordered: bool = True) -> Groups:
     return Groups(gid, ng, rep)
 
 
+_NAN_KEY = ("NaN",)
+
+
+def _key_values(k) -> list:
+    """A key column's values as the hashes group them: every NaN is one key (-0.0 == 0.0 already holds, and both
+    hash alike as dict keys)."""
+    vals = k.to_pylist()
+    if isinstance(getattr(k, "data", None), torch.Tensor) and k.data.is_floating_point():
+        vals = [_NAN_KEY if (v is not None and v != v) else v for v in vals]
+    return vals
+
+
 def _exact_groups(keys, device) -> Groups:
-    cols = [k.to_pylist() for k in keys]
+    cols = [_key_values(k) for k in keys]
     n = keys[0].length
     seen = {}
     gid = []
@@ -141,6 +156,18 @@ def _exact_groups(keys, device) -> Groups:
 
 
 _OPS = {"sum": 0, "min": 1, "max": 2, "count": 3}
+_ORD_NAN = 0x7ff8000000000000                                          # f64_ordered(NaN): the greatest
+_ORD_NEG_INF = (0xfff0000000000000 - (1 << 64)) ^ 0x7fffffffffffffff   # f64_ordered(-inf): the least
+
+
+def _f64_to_ordered(x: torch.Tensor) -> torch.Tensor:
+    """Doubles as int64 keys of their total order (hash_groupby.hip f64_ordered)."""
+    b = torch.where(x != x, torch.full_like(x, float("nan")), x).view(torch.int64)
+    return torch.where(b < 0, b ^ 0x7FFFFFFFFFFFFFFF, b)
+
+
+def _f64_from_ordered(k: torch.Tensor) -> torch.Tensor:
+    return torch.where(k < 0, k ^ 0x7FFFFFFFFFFFFFFF, k).view(torch.float64)
 
 
 def _agg_raw(groups: Groups, data: Optional[torch.Tensor], valid: Optional[torch.Tensor], op: str,
@@ -166,6 +193,12 @@ def _agg_raw(groups: Groups, data: Optional[torch.Tensor], valid: Optional[torch
             0, gid, torch.ones_like(gid))
     if op == "sum":
         return torch.zeros(ng, dtype=data.dtype, device=device).scatter_add_(0, gid, data)
+    if op in ("min", "max") and data.dtype == torch.float64:
+        # the total order of the device paths (hash_groupby.hip f64_ordered): -0.0 < 0.0, NaN greatest; a group
+        # without rows keeps the order's greatest (MIN) or least (MAX) value
+        k = _f64_to_ordered(data)
+        init = torch.full((ng,), _ORD_NAN if op == "min" else _ORD_NEG_INF, dtype=torch.int64, device=device)
+        return _f64_from_ordered(init.scatter_reduce(0, gid, k, "amin" if op == "min" else "amax"))
     if op == "min":
         init = torch.full((ng,), float("inf") if data.dtype == torch.float64 else 2**63 - 1, dtype=data.dtype,
                           device=device)
@@ -290,10 +323,6 @@ _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096
 _MAX_SLOTS = 64
-
-
-def _f64_from_ordered(k: torch.Tensor) -> torch.Tensor:
-    return torch.where(k < 0, k ^ 0x7FFFFFFFFFFFFFFF, k).view(torch.float64)
 
 
 def aggregate_many(groups: Groups, reqs, n: int):

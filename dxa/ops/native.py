@@ -56,6 +56,7 @@ _SIGS = {
     "dxa_table_insert": [c_p, c_i64, c_p, c_i64, c_p, c_p],
     "dxa_group_ids": [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p],
     "dxa_verify_i64": [c_p, c_p, c_p, c_p, c_i64, c_p, c_p],
+    "dxa_verify_f64": [c_p, c_p, c_p, c_p, c_i64, c_p, c_p],
     "dxa_verify_str": [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p],
     "dxa_aggregate": [c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p],
     "dxa_aggregate_multi": [c_p, c_i64, c_i32, c_i32, c_p, c_i32, c_p, c_p, c_p],
