@@ -950,8 +950,13 @@ def _paned_aggregate(sel: A.Select, t, alias: str, ctx) -> Optional[Table]:
             _collect_aggs(e, ctx, aggs)
         if sel.having is not None:
             _collect_aggs(sel.having, ctx, aggs)
-        ok = bool(aggs or sel.group_by) and not any(W.window_calls(e) for e, _ in items) and \
-            D.decomposable(aggs, ctx)
+        ok = bool(aggs or sel.group_by) and not any(W.window_calls(e) for e, _ in items)
+        # COUNT(DISTINCT x) has no mergeable partial, but the dense ring answers it (window_dense.py): a statement
+        # whose aggregates are decomposable apart from one-argument distinct counts is tried there and nowhere else
+        dcounts = {k: c for k, c in aggs.items() if c.distinct and c.name == "count" and len(c.args) == 1 and
+                   not c.star and c.name not in ctx.udafs}
+        dense_only = bool(dcounts)
+        ok = ok and D.decomposable({k: c for k, c in aggs.items() if k not in dcounts}, ctx)
         exprs = [e for e, _ in items] + list(sel.group_by) + ([sel.where] if sel.where is not None else []) + (
             [sel.having] if sel.having is not None else [])
         cacheable = True
@@ -961,11 +966,13 @@ def _paned_aggregate(sel: A.Select, t, alias: str, ctx) -> Optional[Table]:
                         node.name in ctx.udfs and not getattr(ctx.udfs[node.name], "deterministic", False))):
                     cacheable = False
         fp = repr((alias, [e.key() for e in exprs], sel.where is not None, [nm for _, nm in items]))
-        plan_ent = plans[pkey] = (sel, ok, items, aggs, cacheable, fp)
-    _, ok, items, aggs, cacheable, fp = plan_ent
+        plan_ent = plans[pkey] = (sel, ok, items, aggs, cacheable, fp, dense_only)
+    _, ok, items, aggs, cacheable, fp, dense_only = plan_ent
     if not ok:
         return None
-    if cacheable and sel.group_by:
+    if dense_only and (not cacheable or (P.active() and t.dist != P.REPLICATED)):
+        return None                 # the generic path (no partials exist for a distinct count)
+    if cacheable and (sel.group_by or dense_only):
         # the dense ring (persistent group dictionary + per-pane accumulator rows in HBM, window_dense.py): one
         # combine kernel and one status read per batch instead of concatenating and re-grouping partial tables
         from .window_dense import dense_answer, dense_partials
@@ -993,6 +1000,8 @@ def _paned_aggregate(sel: A.Select, t, alias: str, ctx) -> Optional[Table]:
             if got is not None:
                 out_keys, finals, ng, gexprs = got
                 return _paned_output(sel, items, out_keys, finals, ng, gexprs, proto.device, P.REPLICATED, ctx)
+    if dense_only:
+        return None                 # the dense state declined or is disabled: the generic path, never pane partials
     state = {}
 
     def pane_partial(pane, full):

@@ -16,7 +16,7 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
   synchronisation — and builds the output columns as views of the dictionary and the finished aggregates.
 
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over non-decimal numeric,
-boolean or timestamp arguments, with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
+boolean or timestamp arguments (and COUNT(DISTINCT x), below), with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
 exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
 reports a hash collision or an over-long string key — is answered by the paned path, which stays the reference
@@ -33,6 +33,25 @@ whose live set sits just under ``DENSE_GROUPS_MAX`` rebuilds as often as a few n
 in ``DenseWindow.rebuilds``.  A rebuild is local to a rank and issues no collective: with N ranks a rank that
 rebuilds (or falls back) still hands ``dense_partials``' caller a partial table or None, and the caller's exchange is
 the same either way, so the ranks stay in step.
+
+**COUNT(DISTINCT x)** (one argument, any key-column type the dictionary holds; up to ``MAX_DISTINCT`` different
+arguments per statement) is a count of live (group, x) pairs, and "live" is an OR over the window's panes — the
+shape the ring already keeps for groups.  Each distinct argument has a ``PairState``: a second persistent dictionary
+keyed by (group id, x) — filled by the same insert kernel, with the ids the group insert just drew as key column 0;
+rows sent to the dump row and rows whose x is NULL are masked out — and a presence ring ``uint8 [ring slot][pair]``:
+a pane entering a slot zeroes the slot's row and stores 1 for each of its pairs; complete blocks are ORed into the
+block slot the accumulators use.  Per batch ``win_distinct_fold_kernel`` runs between the combine and the keep
+pass: it ORs the window's slots per pair and adds the live pairs into a count word of their group's combined row
+that no pane accumulates into, so the emit kernel finishes it like any count.  The pair statuses (counter, flags)
+travel in the same tensor as the group status: still one read per batch.  When either kind of dictionary is full
+the dirty panes are dropped from both rings; a full group dictionary is renumbered as above and every pair state
+after it (its column 0 mapped old id → new id; a live pair has rows in a held pane, so its group is live too), a
+full pair dictionary alone is rebuilt over the pairs with a byte set in a held pane slot and grows by the same
+policy between ``DENSE_PAIRS`` and ``DENSE_PAIRS_MAX`` ("pair dictionary full" beyond that).  A statement without
+GROUP BY that has such a distinct count runs as one group under a constant key that is not emitted; when nothing in
+the window passes its WHERE the one output row (counts 0, the rest NULL) is built once the status says no group was
+kept.  A distinct count has no mergeable partial: with N ranks it is answered here only over a replicated view, and
+a statement the ring declines goes to the generic path (the materialised window), never to the pane partials.
 """
 from __future__ import annotations
 
@@ -53,6 +72,17 @@ DENSE_GROUPS = 1 << 16            # initial dictionary capacity per statement (g
 DENSE_GROUPS_MAX = 1 << 20        # the capacity grows to this at most (win_compact_kernel's single-workgroup scan)
 SCRATCH_SLOTS = 4                 # ring slots for panes only partly inside a window (re-aggregated every batch)
 BLOCK = 16                        # consecutive in-window panes pre-combined into one block slot, once
+DENSE_PAIRS = 1 << 16             # initial capacity of a COUNT(DISTINCT x) pair dictionary ((group, x) pairs with ids)
+DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring is one byte per ring slot and pair)
+MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
+N.register_sigs({
+    "dxa_win_pairfold_size": [],
+    "dxa_win_pair_prep": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
+    "dxa_win_pair_mark": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_i64, N.c_i32, N.c_p],
+    "dxa_win_pair_or_block": [N.c_p, N.c_i64, N.c_p, N.c_i32, N.c_i32, N.c_p],
+    "dxa_win_answer_distinct": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p,
+                                N.c_p, N.c_p, N.c_p, N.c_p],
+})
 N.register_sigs({"dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p]})
 _SUPPORTED = {"count", "sum", "min", "max", "avg", "mean"}
 
@@ -89,6 +119,15 @@ class _EmitArgs(ctypes.Structure):
                 ("out_idx", ctypes.c_void_p), ("scal", ctypes.c_void_p), ("gcap", ctypes.c_int32)]
 
 
+class _PairFold(ctypes.Structure):
+    _fields_ = [("pres", ctypes.c_void_p), ("pitch", ctypes.c_int64), ("parent", ctypes.c_void_p),
+                ("pscal", ctypes.c_void_p), ("pcap", ctypes.c_int32), ("word", ctypes.c_int32)]
+
+
+class _PairFolds(ctypes.Structure):
+    _fields_ = [("p", _PairFold * MAX_DISTINCT), ("n", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -99,7 +138,8 @@ def _sizes() -> List[int]:
         N.lib().dxa_win_sizes(out)
         _SIZES = list(out)
         if _SIZES[0] != ctypes.sizeof(_KeyCols) or _SIZES[1] != ctypes.sizeof(_DictCols) or \
-                N.lib().dxa_win_emit_size() != ctypes.sizeof(_EmitArgs):
+                N.lib().dxa_win_emit_size() != ctypes.sizeof(_EmitArgs) or \
+                N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds):
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
@@ -109,12 +149,23 @@ class Ineligible(Exception):
 
 
 def _requests(aggs: Dict):
-    """[(agg key, func, arg expr or None)] or Ineligible."""
+    """[(agg key, func, arg expr or None)] or Ineligible.  ``COUNT(DISTINCT x)`` with one argument is the func
+    "dcount"; every other DISTINCT aggregate is ineligible, and so are more than ``MAX_DISTINCT`` different
+    distinct arguments."""
     out = []
+    dargs = set()
     for ak, call in aggs.items():
         name = call.name
-        if call.distinct or name not in _SUPPORTED:
+        if name not in _SUPPORTED:
             raise Ineligible(name)
+        if call.distinct:
+            if name != "count" or call.star or len(call.args) != 1:
+                raise Ineligible(f"{name} distinct")
+            dargs.add(call.args[0].key())
+            if len(dargs) > MAX_DISTINCT:
+                raise Ineligible("too many distinct arguments")
+            out.append((ak, "dcount", call.args[0]))
+            continue
         if call.star or (name == "count" and not call.args):
             out.append((ak, "count_star", None))
             continue
@@ -139,14 +190,144 @@ def _table_slots(gcap: int) -> int:
     return 1 << max(10, (2 * gcap - 1).bit_length())
 
 
+def _pitch(pcap: int) -> int:
+    """Bytes of one presence row: a byte per pair and the dump row, padded to the fold's 16-byte loads."""
+    return (pcap + 1 + 15) // 16 * 16
+
+
+def _distinct_arg(c):
+    """A COUNT(DISTINCT x) argument as a pair-dictionary key column (what ``accumulate`` accepts as a group key)."""
+    c = materialize(c)
+    if isinstance(c, ConstColumn):
+        c = c.materialize()
+    if isinstance(c, PrimColumn):
+        if is_decimal(c.dtype) or c.data.dim() != 1:
+            raise Ineligible("argument type")
+        if c.data.dtype == torch.float32:
+            return PrimColumn(c.dtype, c.data.to(torch.float64), c.valid)
+        if c.data.dtype not in (torch.int64, torch.float64):
+            return PrimColumn(c.dtype, c.data.to(torch.int64), c.valid)
+        return c
+    if type(c) is not StrColumn:
+        raise Ineligible("argument type")
+    return c
+
+
+class PairState:
+    """One distinct argument of a statement: the persistent dictionary of its (group id, x) pairs and the presence
+    ring ``pres`` — ``uint8 [ring slots][pitch]``, 1 where the slot's pane has a row of the pair.  ``pcap``: the
+    dictionary's current capacity; ``rebuilds``: how often it was rebuilt (recycled, grown, or renumbered because
+    the group dictionary was)."""
+
+    def __init__(self, owner: "DenseWindow", k: int, arg_key):
+        self.owner = owner
+        self.arg_key = arg_key
+        self.pcap = DENSE_PAIRS
+        self.pmax = max(DENSE_PAIRS_MAX, DENSE_PAIRS)
+        self.rebuilds = 0
+        self.full = False               # the last status' "pair dictionary full"
+        self.scal_ptr = owner.scal.data_ptr() + 16 * (1 + k)      # this state's counter and flags in the status
+        self.word = -1
+        self.keys = self.pres = None
+        self._alloc_table(self.pcap)
+        N.call("dxa_win_init", N.ptr(self.htab), N.ptr(self.gid_of_slot), self.hcap, N.stream_handle(owner.device))
+
+    @property
+    def pitch(self) -> int:
+        return _pitch(self.pcap)
+
+    def _alloc_table(self, pcap: int) -> None:
+        self.hcap = _table_slots(pcap)
+        self.htab = torch.empty(self.hcap, dtype=torch.int64, device=self.owner.device)
+        self.gid_of_slot = torch.empty(self.hcap, dtype=torch.int32, device=self.owner.device)
+
+    def _bytes(self, pcap: int) -> int:
+        o = self.owner
+        x = 8 + 1 if self.keys is None or self.keys[1][1] != 2 else _sizes()[2] + 4 + 1
+        return (o.R + o.NB) * _pitch(pcap) + (pcap + 1) * (9 + x) + 12 * _table_slots(pcap)
+
+    def build(self, x, word: int) -> None:
+        """Key columns (parent id, x) and the zeroed presence ring, once the first pane shows x's type."""
+        o = self.owner
+        kind = 2 if isinstance(x, StrColumn) else 1 if x.data.dtype == torch.float64 else 0
+        self.word = word
+        self.keys, self.dictcols = o._alloc_keys([("long", 0), (x.dtype, kind)], self.pcap)
+        self.pres = torch.zeros((o.R + o.NB, self.pitch), dtype=torch.uint8, device=o.device)
+
+    def insert(self, gid: torch.Tensor, n: int, x, slot_idx: int, st) -> None:
+        """The pane's rows into the pair dictionary (the group insert kernel, with the rows' group ids as key
+        column 0) and the pairs they drew into presence row ``slot_idx``."""
+        o = self.owner
+        dev = o.device
+        gid64 = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        keep = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        pid = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        v = N.u8(x.valid)
+        if v is not None:
+            v = v.contiguous()
+        N.call("dxa_win_pair_prep", N.ptr(gid), n, o.gcap, N.ptr(v), N.ptr(gid64), N.ptr(keep), st)
+        kc = key_cols([PrimColumn("long", gid64), x])
+        if kc is None:
+            raise Ineligible("argument columns")
+        kc.ncols, kc.n = 2, n
+        N.call("dxa_win_insert_fused", ctypes.addressof(kc), ctypes.addressof(self.dictcols), N.ptr(keep),
+               N.ptr(self.htab), self.hcap, N.ptr(self.gid_of_slot), self.scal_ptr, N.ptr(pid), st)
+        N.call("dxa_win_pair_mark", N.ptr(pid), n, self.pcap, N.ptr(self.pres), self.pitch, slot_idx, st)
+
+    def rebuild(self, slots: List[int], remap: Optional[torch.Tensor], grow: bool) -> None:
+        """Renumber the pairs over those with a byte set in the held pane slots ``slots`` (``DenseWindow.rebuild``
+        dropped the dirty panes and cleared the block cache): key columns and presence columns gathered into
+        fresh tensors — column 0 through ``remap`` when the group ids were renumbered; a live pair has rows in a
+        held pane, so its group is live too — and the table refilled.  Off the hot path: torch indexing and one
+        host read (the live count).  Raises ``Ineligible`` ("pair dictionary full" / "memory")."""
+        o = self.owner
+        dev = o.device
+        if grow and self.pcap >= self.pmax:
+            raise Ineligible("pair dictionary full")
+        sl = torch.tensor(slots, dtype=torch.int64, device=dev)
+        idx = torch.nonzero(self.pres[sl, :self.pcap].any(dim=0)).flatten()
+        live = int(idx.shape[0])
+        target = _target_capacity(live, self.pcap, self.pmax)
+        if grow:
+            target = min(max(target, 2 * self.pcap), self.pmax)
+        try:
+            if target != self.pcap and self._bytes(target) > torch.cuda.mem_get_info(dev)[0] // 2:
+                raise Ineligible("memory")
+            keys, dc = o._alloc_keys([(k[0], k[1]) for k in self.keys], target)
+            pres = torch.zeros((o.R + o.NB, _pitch(target)), dtype=torch.uint8, device=dev)
+            if target != self.pcap:
+                self._alloc_table(target)
+        except torch.cuda.OutOfMemoryError:
+            raise Ineligible("memory") from None
+        kw = _sizes()[2]
+        for (_dt, kind, vals, lens, valid), (_d2, _k2, nvals, nlens, nvalid) in zip(self.keys, keys):
+            if kind == 2:
+                nvals.view(target + 1, kw)[:live] = vals.view(self.pcap + 1, kw)[idx]
+                nlens[:live] = lens[idx]
+            else:
+                nvals[:live] = vals[idx]
+            nvalid[:live] = valid[idx]
+        if remap is not None:
+            parents = keys[0][2]
+            parents[:live] = remap[parents[:live].clamp(0, remap.shape[0] - 1)]
+        pres[sl, :live] = self.pres[sl][:, idx]
+        self.keys, self.dictcols, self.pres, self.pcap = keys, dc, pres, target
+        N.call("dxa_win_rehash", ctypes.addressof(dc), N.ptr(self.htab), N.ptr(self.gid_of_slot), self.hcap, live,
+               self.scal_ptr, N.stream_handle(dev))
+        self.full = False
+        self.rebuilds += 1
+
+
 class DenseWindow:
     """Persistent state of one windowed statement (one fingerprint) on one device.  ``gcap``: the dictionary's
     current capacity; ``rebuilds``: how often it was rebuilt; ``disabled_reason``: None while the statement is
     answered here, else why it went to the paned path for good."""
 
-    def __init__(self, device, reqs, ring_slots: int):
+    def __init__(self, device, reqs, ring_slots: int, global_form: bool = False):
         self.device = device
         self.reqs = reqs
+        self.global_form = global_form  # no GROUP BY: one group under a constant key that is not emitted
+        self._rebuilt: set = set()      # dictionaries rebuilt so far in the current dense_answer call
         self.gcap = DENSE_GROUPS
         self.gmax = max(DENSE_GROUPS_MAX, DENSE_GROUPS)
         self.rebuilds = 0
@@ -170,7 +351,12 @@ class DenseWindow:
         # cache) and one for the answer, a rebuild one more, and every pass and every rebuild ends in a status read
         # that drains the stream before the next begins — so NB + 2 rows are never rewritten while a copy is queued
         self._pinned = torch.empty((self.NB + 2, self.R), dtype=torch.int32, pin_memory=True)
-        self._scal_pin = [torch.empty(4, dtype=torch.int32, pin_memory=True) for _ in range(2)]
+        dkeys = []
+        for _, func, arg in reqs:
+            if func == "dcount" and arg.key() not in dkeys:
+                dkeys.append(arg.key())
+        nstat = 4 + 4 * len(dkeys)      # the outer status, then counter / flags / 2 pads per pair state
+        self._scal_pin = [torch.empty(nstat, dtype=torch.int32, pin_memory=True) for _ in range(2)]
         self._scal_k = 0
         self._pin_k = 0
         cap = _table_slots(self.gcap)
@@ -178,8 +364,10 @@ class DenseWindow:
         dev = device
         self.htab = torch.empty(cap, dtype=torch.int64, device=dev)
         self.gid_of_slot = torch.empty(cap, dtype=torch.int32, device=dev)
-        self.scal = torch.zeros(4, dtype=torch.int32, device=dev)     # groups, bad flags, kept, pad
+        self.scal = torch.zeros(nstat, dtype=torch.int32, device=dev)     # groups, bad flags, kept, pad[, pair states]
         N.call("dxa_win_init", N.ptr(self.htab), N.ptr(self.gid_of_slot), cap, N.stream_handle(dev))
+        # one pair state per different COUNT(DISTINCT x) argument, in order of first appearance
+        self.pairs: List[PairState] = [PairState(self, k, dk) for k, dk in enumerate(dkeys)]
         self.keys = None                # dictionary key columns, built with the layout
         self.ring = None
 
@@ -220,9 +408,9 @@ class DenseWindow:
         total = (self.R + self.NB + 1) * rows * self.stride * 8 + 9 * gcap + 12 * _table_slots(gcap)
         for _dt, kind, *_ in self.keys:
             total += rows * ((kw + 4 if kind == 2 else 8) + 1)
-        return total
+        return total + sum(ps._bytes(ps.pcap) for ps in self.pairs)
 
-    def _build_layout(self, key_cols_in: List, args: Dict):
+    def _build_layout(self, key_cols_in: List, args: Dict, dargs: Dict):
         if not 1 <= len(key_cols_in) <= MAX_KEY_COLS:
             raise Ineligible("key count")
         kinds = [(k.dtype, 2 if isinstance(k, StrColumn) else 1 if k.data.dtype == torch.float64 else 0)
@@ -246,6 +434,11 @@ class DenseWindow:
         for ak, func, arg in self.reqs:
             if func == "count_star":
                 plan.append((ak, "count", star, None, None))
+                continue
+            if func == "dcount":
+                # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
+                # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
+                plan.append((ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None))
                 continue
             col = args[arg.key()]
             ck = arg.key()
@@ -307,6 +500,8 @@ class DenseWindow:
         self.line_ops_dev = self.line_ops_t.to(self.device)
         try:
             self.ring, self.acc, self.keep, self.out_idx = self._alloc_ring(self.gcap)
+            for ps in self.pairs:
+                ps.build(dargs[ps.arg_key], where[keyed[("dcount", ps.arg_key)]])
         except torch.cuda.OutOfMemoryError:
             self.layout = None
             raise Ineligible("memory") from None
@@ -330,7 +525,13 @@ class DenseWindow:
         has been queued (checked against half the free memory first).  Block slots are not remapped: the block
         cache is cleared and complete blocks are combined again on next use."""
         self.rebuild_pending = False
-        if grow and self.gcap >= self.gmax:
+        # with distinct counts the status says which dictionaries are full: the group dictionary is rebuilt only
+        # when it is, a pair dictionary when it is or when the group ids it is keyed by were renumbered.  ``grow``
+        # applies to a dictionary that this call already rebuilt once.
+        outer_full = bool(self.bad & 2) or not self.pairs
+        done = self._rebuilt
+        grow_outer = grow and (not self.pairs or "outer" in done)
+        if outer_full and grow_outer and self.gcap >= self.gmax:
             raise Ineligible("dictionary full")
         # panes accumulated since the last clean status sent some rows to the dump row: the caller's pane loop
         # accumulates them again after the rebuild
@@ -341,10 +542,22 @@ class DenseWindow:
         self.dirty = []
         self.blocks.clear()
         self.release_expired(retained)
+        slots = sorted(e[0] for e in self.slot_of.values())
+        remap = None
+        if outer_full:
+            remap = self._rebuild_groups(slots, grow_outer)
+            done.add("outer")
+        for ps in self.pairs:
+            if outer_full or ps.full:
+                ps.rebuild(slots, remap, grow and ps in done)
+                done.add(ps)
+
+    def _rebuild_groups(self, slots: List[int], grow: bool) -> Optional[torch.Tensor]:
+        """``rebuild``'s renumbering of the group dictionary over the held pane slots ``slots``.  With pair states:
+        → the map old group id → new id (-1: dropped), for their key column 0."""
         L = self.layout
         dev = self.device
         st = N.stream_handle(dev)
-        slots = sorted(e[0] for e in self.slot_of.values())
         N.call("dxa_win_live", N.ptr(self.ring), self.gcap, self.stride, N.ptr(self._dev_slots(slots)), len(slots),
                N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
                N.ptr(self.out_idx), st)
@@ -374,10 +587,15 @@ class DenseWindow:
                live, st)
         N.call("dxa_win_rehash", ctypes.addressof(dc), N.ptr(htab), N.ptr(gid_of_slot), hcap, live, N.ptr(self.scal),
                st)
+        remap = None
+        if self.pairs:
+            remap = torch.full((self.gcap + 1,), -1, dtype=torch.int64, device=dev)
+            remap[self.out_idx[:live]] = torch.arange(live, dtype=torch.int64, device=dev)
         self.keys, self.dictcols, self.gcap = keys, dc, target
         self.ring, self.acc, self.keep, self.out_idx = ring, acc, keep, out_idx
         self.htab, self.gid_of_slot, self.hcap = htab, gid_of_slot, hcap
         self.rebuilds += 1
+        return remap
 
     # ---- one pane into one ring slot ----------------------------------------------------------------------------
     def accumulate(self, table, slot_idx: int, alias, where, gexprs, ctx):
@@ -400,8 +618,14 @@ class DenseWindow:
             elif not isinstance(k, StrColumn) or type(k) is not StrColumn:
                 raise Ineligible("key type")
             keys.append(k)
-        args = {}
+        if self.global_form:
+            keys = [PrimColumn("long", torch.zeros(n, dtype=torch.int64, device=self.device))]
+        args, dargs = {}, {}
         for _, func, arg in self.reqs:
+            if func == "dcount":
+                if arg.key() not in dargs:
+                    dargs[arg.key()] = _distinct_arg(evaluate(arg, scope, ctx))
+                continue
             if arg is None or arg.key() in args:
                 continue
             c = evaluate(arg, scope, ctx)
@@ -411,11 +635,16 @@ class DenseWindow:
                 raise Ineligible("argument type")
             args[arg.key()] = c
         if self.layout is None:
-            self._build_layout(keys, args)
+            self._build_layout(keys, args, dargs)
         else:
             for (dt, kind, *_), k in zip(self.keys, keys):
                 if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
                     raise Ineligible("key types changed")
+            for ps in self.pairs:
+                dt, kind = ps.keys[1][:2]
+                k = dargs[ps.arg_key]
+                if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
+                    raise Ineligible("argument types changed")
         L = self.layout
         dev = self.device
         st = N.stream_handle(dev)
@@ -433,6 +662,9 @@ class DenseWindow:
                 spec += [0, 0, -1]
                 continue
             key, kind, _op = L["slots"][i]
+            if key[0] == "dcount":
+                spec += [0, 0, -1]
+                continue
             if key[1] is None:
                 spec += [0, 0, kind]
                 continue
@@ -456,6 +688,8 @@ class DenseWindow:
         ring_ptr = self.ring[slot_idx].data_ptr()
         N.call("dxa_aggregate_multi", N.ptr(gid), n, self.gcap + 1, L["nslots"], spec_t.data_ptr(),
                len(L["line_ops"]), self.line_ops_t.data_ptr(), ring_ptr, st)
+        for ps in self.pairs:
+            ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
 
     def _dev_slots(self, slots: List[int]) -> torch.Tensor:
@@ -479,8 +713,12 @@ class DenseWindow:
             raise Ineligible("block slots")
         dst = free[0]
         member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
-        N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(self._dev_slots(member_slots)),
-               len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.stream_handle(self.device))
+        slots_dev = self._dev_slots(member_slots)
+        st = N.stream_handle(self.device)
+        N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
+               len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), st)
+        for ps in self.pairs:       # the members' presence rows ORed into the same block slot of the presence ring
+            N.call("dxa_win_pair_or_block", N.ptr(ps.pres), ps.pitch, N.ptr(slots_dev), len(member_slots), dst, st)
         self.blocks[bid] = (members, dst, list(mem))
         return dst
 
@@ -498,9 +736,21 @@ class DenseWindow:
         slots_dev = self._dev_slots(slots)
         fin = L["pspec_of"](partial_proto) if partial_proto is not None else L["fin"]
         e, bufs = self._emit_args(fin)
-        N.call("dxa_win_answer", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
-               N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
-               N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols), st)
+        if self.pairs:
+            # the same launches with one distinct fold per pair state between the combine and the keep pass
+            folds = _PairFolds()
+            for k, ps in enumerate(self.pairs):
+                folds.p[k] = _PairFold(ps.pres.data_ptr(), ps.pitch, ps.keys[0][2].data_ptr(), ps.scal_ptr, ps.pcap,
+                                       ps.word)
+            folds.n = len(self.pairs)
+            N.call("dxa_win_answer_distinct", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
+                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
+                   ctypes.addressof(folds), st)
+        else:
+            N.call("dxa_win_answer", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
+                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols), st)
         if not defer:
             # the statement's one synchronising read
             return self._finish(self.scal.tolist(), bufs, fin, partial_proto)
@@ -517,15 +767,33 @@ class DenseWindow:
 
     def _finish(self, status, bufs, fin, partial_proto):
         L = self.layout
-        ng_all, bad, nout, _ = status
+        ng_all, bad, nout = status[:3]
+        for k, ps in enumerate(self.pairs):
+            # a pair dictionary's collision / over-long value joins the outer flags; its "full" is flag 8 here
+            pflags = status[4 + 4 * k + 1]
+            ps.full = bool(pflags & 2)
+            bad |= (pflags & 5) | (8 if ps.full else 0)
         self.bad = bad
         if bad:
-            # a full dictionary and nothing else: rebuilt before the next answer (dense_answer); a collision or an
+            # full dictionaries and nothing else: rebuilt before the next answer (dense_answer); a collision or an
             # over-long key (never cleared on the device) sends the statement to the paned path for good
-            self.rebuild_pending = bad == 2
+            self.rebuild_pending = not bad & 5
             return None
         self.dirty = []
         okey, olen, ovalid, dst, dvalid = bufs
+        if self.global_form and nout == 0:
+            # no row passed the WHERE anywhere in the window: Spark's one row — counts 0, everything else NULL
+            finals = {}
+            for ak, kind, s, c, dt in L["plan"]:
+                if kind == "count":
+                    finals[ak] = PrimColumn("long", torch.zeros(1, dtype=torch.int64, device=self.device))
+                else:
+                    td = torch.float64 if kind in ("avg", "f64") or dt == "double" else \
+                        torch.bool if dt == "boolean" else torch.int64
+                    finals[ak] = PrimColumn("double" if kind == "avg" else dt,
+                                            torch.zeros(1, dtype=td, device=self.device),
+                                            torch.zeros(1, dtype=torch.bool, device=self.device))
+            return [], finals, 1
         out_keys = []
         for j, (dt, kind, vals, lens, valid) in enumerate(self.keys):
             v = ovalid[j, :nout].view(torch.bool)
@@ -555,7 +823,7 @@ class DenseWindow:
                 finals[ak] = PrimColumn(dt, v.view(torch.float64), ok)
             else:
                 finals[ak] = PrimColumn(dt, v.to(torch.bool) if dt == "boolean" else v, ok)
-        return out_keys, finals, nout
+        return ([] if self.global_form else out_keys), finals, nout
 
     def _emit_args(self, fin):
         """The emit kernel's descriptor and this batch's output buffers ([gcap]-strided, fresh per batch: the
@@ -649,7 +917,12 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
     from .expr import Scope
     store = t.store
     dev = t._device
-    if dev.type != "cuda" or not sel.group_by or (partial_proto is None and P.active() and t.dist != P.REPLICATED):
+    distinct = any(c.distinct for c in aggs.values())
+    if dev.type != "cuda" or (partial_proto is None and P.active() and t.dist != P.REPLICATED):
+        return None
+    if not sel.group_by and not distinct:   # a global statement without a distinct count keeps the paned path
+        return None
+    if distinct and partial_proto is not None:      # a distinct count has no mergeable partial
         return None
     states = store.__dict__.setdefault("_dense", {})
     state = states.get(fp)
@@ -662,13 +935,17 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
         if state is None:
             iv = max(1, store.interval_us)
             panes = store.conf.max_window_us // iv + store.conf.watermark_us // iv + 4
-            state = states[fp] = DenseWindow(dev, _requests(aggs), max(panes, len(pieces) + 2))
+            state = states[fp] = DenseWindow(dev, _requests(aggs), max(panes, len(pieces) + 2),
+                                             global_form=not sel.group_by)
+        state._rebuilt = set()
         proto = pieces[0][0].table
         gexprs = [_resolve_group_expr(g, Scope.of_table(proto, alias), items) for g in sel.group_by]
         # A status that reads "dictionary full" (in this call, or in the deferred completion of the last one) is
         # answered by a rebuild and another pass over the window's panes, which accumulates the dropped panes
         # again.  Every rebuild after the first in one call doubles the capacity or gives up, so the loop ends
-        # within log2(DENSE_GROUPS_MAX / DENSE_GROUPS) + 2 passes.
+        # within log2(DENSE_GROUPS_MAX / DENSE_GROUPS) + 2 passes.  (With pair states: every pass rebuilds at least
+        # one full dictionary, and a dictionary's second rebuild in one call doubles it or gives up — the same
+        # bound per dictionary.)
         rebuilt = False
         while True:
             if state.rebuild_pending:
@@ -704,13 +981,17 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
 
 
 def _flag_reason(bad: int) -> str:
-    return "hash collision" if bad & 1 else "key too long" if bad & 4 else "dictionary full"
+    # an over-long key is stored with length 0, so later rows of that key also compare unequal (flag 1): 4 first
+    return "key too long" if bad & 4 else "hash collision" if bad & 1 else "dictionary full" if bad & 2 or not bad \
+        else "pair dictionary full"
 
 
 def _disable(state, reason: str) -> None:
     state.disabled = True
     state.disabled_reason = reason
     state.ring = state.acc = None
+    for ps in state.pairs:
+        ps.pres = None
 
 
 def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defer: bool):

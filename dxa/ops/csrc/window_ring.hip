@@ -22,6 +22,9 @@
 // finds the groups that still have rows in the panes the ring holds, win_remap_dict / win_remap_slot renumber them
 // densely in the key columns and in every held pane slot, win_rehash refills the cleared table (dxa_win_live …
 // dxa_win_rehash below; the policy is the host's, dxa/engine/window_dense.py DenseWindow.rebuild).
+// COUNT(DISTINCT x) rides on the same ring: a pair dictionary keyed by (group id, x) and one presence byte per ring
+// slot and pair (win_pair_mark), ORed over the window and added into the combined rows between steps 3 and 4
+// (win_distinct_fold) — see the section before the entry points.
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -428,6 +431,108 @@ __global__ __launch_bounds__(256) void win_rehash_kernel(const DictCols d, uint6
   }
 }
 
+// ---- COUNT(DISTINCT x) over the window: a distinct count is a count of live (group, x) pairs, and "live" is an OR
+// over the window's panes.  Each distinct argument has a second persistent dictionary keyed by (parent group id, x)
+// — filled by win_insert_kernel itself, with the outer insert's ids widened to int64 as key column 0 — and a
+// presence ring of one byte per (ring slot, pair).  Bytes, not accumulator lines: at 2^20 pairs and ~320 slots the
+// presence ring is ~335 MB where 64-byte lines would be over 20 GB.
+
+constexpr int kMaxPairStates = 4;
+struct PairFold {
+  const uint8_t* pres;     // [ring slots][pitch], pitch a multiple of 16
+  int64_t pitch;
+  const int64_t* parent;   // the pair dictionary's key column 0: each pair's group id
+  const int32_t* pscal;    // the pair dictionary's counter and flags
+  int32_t pcap;
+  int32_t word;            // the count word of the combined row this distinct count is added into
+};
+struct PairFolds {
+  PairFold p[kMaxPairStates];
+  int32_t n;
+  int32_t pad;
+};
+
+// the pair insert's inputs from the outer insert's ids: column 0 (int64) and the row mask — rows the outer insert
+// sent to the dump row (filtered by WHERE, or drawn past the capacity) and rows whose x is NULL create no pair
+__global__ void win_pair_prep_kernel(const int32_t* __restrict__ gid, int64_t n, int32_t gcap,
+                                     const uint8_t* __restrict__ xvalid, int64_t* __restrict__ gid64,
+                                     uint8_t* __restrict__ keep) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t g = gid[i];
+    gid64[i] = g;
+    keep[i] = (g >= 0 && g < gcap && (!xvalid || xvalid[i])) ? 1 : 0;
+  }
+}
+
+// a pane's pairs into its (zeroed) presence row: plain idempotent stores, no atomics
+__global__ void win_pair_mark_kernel(const int32_t* __restrict__ pid, int64_t n, int32_t pcap,
+                                     uint8_t* __restrict__ row) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t p = pid[i];
+    if (p >= 0 && p < pcap) row[p] = 1;
+  }
+}
+
+// a complete block's presence rows ORed into a block slot, 16 pairs per lane; the whole pitch is written, so pairs
+// the dictionary gains later read 0 there
+__global__ __launch_bounds__(256) void win_pair_or_kernel(const uint8_t* __restrict__ pres, int64_t pitch,
+                                                          const int32_t* __restrict__ slots, int32_t nslots,
+                                                          uint8_t* __restrict__ dst) {
+  const int64_t chunks = pitch >> 4;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * blockDim.x) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    for (int s = 0; s < nslots; ++s) {
+      const uint4 w = *(const uint4*)(pres + (int64_t)slots[s] * pitch + (c << 4));
+      v.x |= w.x; v.y |= w.y; v.z |= w.z; v.w |= w.w;
+    }
+    *(uint4*)(dst + (c << 4)) = v;
+  }
+}
+
+// the window's distinct counts into the combined rows (after win_combine, before win_keep / win_emit): a pair is
+// live when any of the window's slots has its byte set; every live pair adds 1.0 to its parent's reserved count
+// word, which win_emit's F_COUNT then finishes like any other count.  A lane owns 16 consecutive pairs (one 16-byte
+// load per slot).  The adds are aggregated in the wave first — one atomic of the popcount per distinct parent per
+// wave and pair position: the global form has every pair under one parent, and every adder on one row runs an order
+// of magnitude below the float-atomic rate.  Counts are integers in f64, so the sums are exact in any order.
+__global__ __launch_bounds__(256) void win_distinct_fold_kernel(const PairFold f, const int32_t* __restrict__ slots,
+                                                                int32_t nslots, const int32_t* __restrict__ scal,
+                                                                int32_t gcap, double* __restrict__ acc,
+                                                                int32_t stride) {
+  int32_t ng = scal[0];
+  if (ng > gcap) ng = gcap;
+  int32_t np = f.pscal[0];
+  if (np > f.pcap) np = f.pcap;
+  const int lane = threadIdx.x & 63;
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  // c0: the wave's first chunk, so the loop (and the ballots in it) is wave-uniform
+  for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane; c0 * 16 < np; c0 += step) {
+    const int64_t p0 = (c0 + lane) * 16;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (p0 < np) {
+      for (int s = 0; s < nslots; ++s) {
+        const uint4 v = *(const uint4*)(f.pres + (int64_t)slots[s] * f.pitch + p0);
+        w[0] |= v.x; w[1] |= v.y; w[2] |= v.z; w[3] |= v.w;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const bool on = p0 + q < np && ((w[q >> 2] >> (8 * (q & 3))) & 0xffu) != 0u;
+      const int64_t par = on ? f.parent[p0 + q] : -1;
+      const bool active = on && par >= 0 && par < ng;
+      const int32_t mine = active ? (int32_t)par : -1;
+      unsigned long long todo = __ballot(active);
+      while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int32_t first = __shfl(mine, lead);
+        const unsigned long long same = __ballot(active && mine == first);
+        if (lane == lead) atomicAdd(acc + (int64_t)first * stride + f.word, (double)__popcll(same));
+        todo &= ~same;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 DXA_API int dxa_win_sizes(int32_t* out) {
@@ -559,5 +664,67 @@ DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const
   if (rc) return rc;
   hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, (hipStream_t)st,
                      *(const EmitArgs*)emit, *(const DictCols*)dictcols);
+  return (int)hipGetLastError();
+}
+
+// ---- COUNT(DISTINCT x): entry points -----------------------------------------------------------------------------
+
+DXA_API int dxa_win_pairfold_size() { return (int)sizeof(PairFolds); }
+
+// column 0 and the row mask of a pane's pair insert (win_pair_prep_kernel)
+DXA_API int dxa_win_pair_prep(const int32_t* gid, int64_t n, int32_t gcap, const uint8_t* xvalid, int64_t* gid64,
+                              uint8_t* keep, void* st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(win_pair_prep_kernel, dim3(dxa_blocks(n, 256)), dim3(256), 0, (hipStream_t)st, gid, n, gcap,
+                     xvalid, gid64, keep);
+  return (int)hipGetLastError();
+}
+
+// a pane entering ring slot ``slot``: the slot's presence row is zeroed, then every row's pair id is marked
+DXA_API int dxa_win_pair_mark(const int32_t* pid, int64_t n, int32_t pcap, uint8_t* pres, int64_t pitch, int32_t slot,
+                              void* st) {
+  hipStream_t s = (hipStream_t)st;
+  if (pitch < (int64_t)pcap + 1 || (pitch & 15) || slot < 0) return (int)hipErrorInvalidValue;
+  uint8_t* row = pres + (int64_t)slot * pitch;
+  hipMemsetAsync(row, 0, (size_t)pitch, s);
+  if (n > 0)
+    hipLaunchKernelGGL(win_pair_mark_kernel, dim3(dxa_blocks(n, 256)), dim3(256), 0, s, pid, n, pcap, row);
+  return (int)hipGetLastError();
+}
+
+// a block of presence rows ORed into slot ``dst`` (not a member), as dxa_win_combine_block does for accumulators
+DXA_API int dxa_win_pair_or_block(uint8_t* pres, int64_t pitch, const int32_t* slots, int32_t nslots, int32_t dst,
+                                  void* st) {
+  if ((pitch & 15) || dst < 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(win_pair_or_kernel, dim3(dxa_blocks(pitch >> 4, 256, 256 * 64)), dim3(256), 0, (hipStream_t)st,
+                     (const uint8_t*)pres, pitch, slots, nslots, pres + (int64_t)dst * pitch);
+  return (int)hipGetLastError();
+}
+
+// dxa_win_answer for a statement with distinct counts: combine, the distinct folds into the combined rows, then keep,
+// compaction and the output rows
+DXA_API int dxa_win_answer_distinct(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots,
+                                    int32_t nslots, const int32_t* line_op, int32_t count_word, int32_t* scal,
+                                    void* acc, uint8_t* keep, int64_t* out_idx, const void* emit,
+                                    const void* dictcols, const void* folds, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  const PairFolds& pf = *(const PairFolds*)folds;
+  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < pf.n; ++k)
+    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
+      return (int)hipErrorInvalidValue;
+  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+  hipMemsetAsync(scal + 2, 0, 4, s);
+  hipLaunchKernelGGL(win_combine_kernel<false>, dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+                     s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
+                     (unsigned long long*)acc);
+  for (int k = 0; k < pf.n; ++k)
+    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
+                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
+  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
+  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *(const EmitArgs*)emit,
+                     *(const DictCols*)dictcols);
   return (int)hipGetLastError();
 }
