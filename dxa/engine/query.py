@@ -1728,8 +1728,13 @@ def _eval_agg(call: A.Call, scope: Scope, groups: G.Groups, ctx) -> Column:
         p = 0.5 if name == "median" else evaluate(call.args[1], scope, ctx)
         return _percentile(groups, arg, p, exact=name in ("percentile", "median"))
     if name in ("count_if",):
+        # a count, so never NULL: over no rows (a global aggregate of an empty input) the sum's NULL is 0, which is
+        # also what the pane partials' merged "cnt" and the dense ring give
         m = predicate_mask(arg)
-        return G.aggregate(groups, PrimColumn("long", m.to(torch.int64)), "sum", n)
+        r = G.aggregate(groups, PrimColumn("long", m.to(torch.int64)), "sum", n)
+        if r.valid is None:
+            return r
+        return PrimColumn("long", torch.where(r.valid.to(torch.bool), r.data, torch.zeros_like(r.data)), None)
     if name in ("bool_and", "every", "bool_or", "any", "some"):
         v = arg
         r = G.aggregate(groups, PrimColumn("long", v.data.to(torch.int64), v.valid),

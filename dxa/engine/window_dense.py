@@ -16,7 +16,8 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
   synchronisation — and builds the output columns as views of the dictionary and the finished aggregates.
 
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over non-decimal numeric,
-boolean or timestamp arguments (and COUNT(DISTINCT x), below), with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
+boolean or timestamp arguments (and COUNT(DISTINCT x) and the variance family, below; count_if; bool_and / every,
+bool_or / any / some), with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
 exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
 reports a hash collision or an over-long string key — is answered by the paned path, which stays the reference
@@ -52,6 +53,17 @@ GROUP BY that has such a distinct count runs as one group under a constant key t
 the window passes its WHERE the one output row (counts 0, the rest NULL) is built once the status says no group was
 kept.  A distinct count has no mergeable partial: with N ranks it is answered here only over a replicated view, and
 a statement the ring declines goes to the generic path (the materialised window), never to the pane partials.
+
+**STDDEV / VARIANCE** (``_VARIANCE``; up to ``MAX_VARIANCE`` different arguments per statement) keep, per pane and
+group, the triple (n, Σx, M2) with M2 = Σ (x − mean)² about the pane's own mean: n and Σx are the count and sum words
+AVG of the same argument uses, M2 is one more word in a line whose combine op (``MA_M2``) only window_ring.hip knows.
+A pane is accumulated in two passes: the fused multi-aggregate, which sees that line as unused f64 words and leaves
+them 0.0, then ``win_m2_kernel``, which reads each row's group mean from the finished slot and adds the squared
+distance.  The combine merges slots with the multi-way form of Chan's update (``distagg._chan_merge``'s formula), so
+a block slot is again a valid triple and nothing is ever computed as Σx² − (Σx)²/n.  A layout without a variance
+argument has no such line and issues exactly the launches it issued before (``dxa_win_answer_m2`` /
+``dxa_win_combine_block_m2`` sit beside the plain entry points as ``dxa_win_answer_distinct`` does).  With N ranks
+the partial states are ("s", "m2", "cnt"), the table ``distagg._partials`` builds.
 """
 from __future__ import annotations
 
@@ -62,8 +74,9 @@ from typing import Dict, List, Optional
 import torch
 
 from ..ops import native as N
-from ..ops.groupby import (_F_AVG, _F_COUNT, _F_F64, _F_F64_ORD, _F_I64, _F_NOT, _MA_ADD_F64, _MA_ADD_U64, _MA_MAX,
-                           _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64, _MV_NOT)
+from ..ops.groupby import (_F_AVG, _F_COUNT, _F_F64, _F_F64_ORD, _F_I64, _F_NOT, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP,
+                           _MA_ADD_F64, _MA_ADD_U64, _MA_M2, _MA_MAX, _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64,
+                           _MV_NOT)
 from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
 from .decimal import is_decimal
@@ -75,6 +88,7 @@ BLOCK = 16                        # consecutive in-window panes pre-combined int
 DENSE_PAIRS = 1 << 16             # initial capacity of a COUNT(DISTINCT x) pair dictionary ((group, x) pairs with ids)
 DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring is one byte per ring slot and pair)
 MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
+MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per statement (window_ring.hip kMaxM2Args)
 N.register_sigs({
     "dxa_win_pairfold_size": [],
     "dxa_win_pair_prep": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
@@ -84,7 +98,20 @@ N.register_sigs({
                                 N.c_p, N.c_p, N.c_p, N.c_p],
 })
 N.register_sigs({"dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p]})
-_SUPPORTED = {"count", "sum", "min", "max", "avg", "mean"}
+N.register_sigs({
+    "dxa_win_m2_size": [],
+    "dxa_win_m2_lds_groups": [],
+    "dxa_win_m2": [N.c_p, N.c_p],
+    "dxa_win_combine_block_m2": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
+    "dxa_win_answer_m2": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
+                          N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
+})
+# the variance family → the finishing kind of its M2 word (window_ring.hip win_emit_kernel)
+_VARIANCE = {"stddev": _F_VAR_SAMP | _F_SQRT, "std": _F_VAR_SAMP | _F_SQRT, "stddev_samp": _F_VAR_SAMP | _F_SQRT,
+             "stddev_pop": _F_VAR_POP | _F_SQRT, "variance": _F_VAR_SAMP, "var_samp": _F_VAR_SAMP,
+             "var_pop": _F_VAR_POP}
+_BOOL = {"bool_and": "min", "every": "min", "bool_or": "max", "any": "max", "some": "max"}
+_SUPPORTED = {"count", "sum", "min", "max", "avg", "mean", "count_if", *_VARIANCE, *_BOOL}
 
 N.register_sigs({
     "dxa_win_live": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
@@ -128,6 +155,17 @@ class _PairFolds(ctypes.Structure):
     _fields_ = [("p", _PairFold * MAX_DISTINCT), ("n", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class _M2Arg(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("cnt", ctypes.c_int32), ("sum", ctypes.c_int32),
+                ("m2", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class _M2Args(ctypes.Structure):
+    _fields_ = [("a", _M2Arg * MAX_VARIANCE), ("gid", ctypes.c_void_p), ("row", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("gcap", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -139,7 +177,8 @@ def _sizes() -> List[int]:
         _SIZES = list(out)
         if _SIZES[0] != ctypes.sizeof(_KeyCols) or _SIZES[1] != ctypes.sizeof(_DictCols) or \
                 N.lib().dxa_win_emit_size() != ctypes.sizeof(_EmitArgs) or \
-                N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds):
+                N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds) or \
+                N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args):
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
@@ -151,9 +190,12 @@ class Ineligible(Exception):
 def _requests(aggs: Dict):
     """[(agg key, func, arg expr or None)] or Ineligible.  ``COUNT(DISTINCT x)`` with one argument is the func
     "dcount"; every other DISTINCT aggregate is ineligible, and so are more than ``MAX_DISTINCT`` different
-    distinct arguments."""
+    distinct arguments.  The variance family keeps its name (``_VARIANCE``), ``bool_and`` / ``every`` are "min" and
+    ``bool_or`` / ``any`` / ``some`` "max" of a boolean result ("bmin" / "bmax"); more than ``MAX_VARIANCE``
+    different variance arguments are ineligible."""
     out = []
     dargs = set()
+    vargs = set()
     for ak, call in aggs.items():
         name = call.name
         if name not in _SUPPORTED:
@@ -171,7 +213,11 @@ def _requests(aggs: Dict):
             continue
         if len(call.args) != 1:
             raise Ineligible(name)
-        out.append((ak, "avg" if name == "mean" else name, call.args[0]))
+        if name in _VARIANCE:
+            vargs.add(call.args[0].key())
+            if len(vargs) > MAX_VARIANCE:
+                raise Ineligible("too many variance arguments")
+        out.append((ak, "avg" if name == "mean" else "b" + _BOOL[name] if name in _BOOL else name, call.args[0]))
     return out
 
 
@@ -211,6 +257,129 @@ def _distinct_arg(c):
     if type(c) is not StrColumn:
         raise Ineligible("argument type")
     return c
+
+
+def plan_layout(reqs, arg_types: Dict) -> Dict:
+    """The accumulator layout of a statement (no device involved).  ``reqs``: ``_requests``' result;
+    ``arg_types[arg key] = (column dtype, is float64)`` of every evaluated non-distinct argument.
+
+    → ``slots`` [(key, agg_multi value kind, combine op)], ``order`` (slot per word, None for padding),
+    ``line_ops`` (combine op per 8-word line), ``plan`` [(agg key, kind, slot, count slot, dtype)], ``fin`` /
+    ``pfin`` (win_emit_kernel's (kind, word, count word) per aggregate / per partial state), ``m2desc`` and
+    ``m2args`` (the variance arguments' words for win_combine_kernel and win_m2_kernel)."""
+    # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
+    slots, keyed = [], {}
+
+    def slot(key, kind, op):
+        s = keyed.get(key)
+        if s is None:
+            s = keyed[key] = len(slots)
+            slots.append((key, kind, op))
+        return s
+
+    star = slot(("count", None), _MV_COUNT, _MA_ADD_F64)
+    plan = []
+    m2_of = {}                      # M2 slot → (count slot, sum slot) of the same argument
+    value_only = set()              # aggregates whose partial is the value alone (distagg._partials: bool_and / bool_or)
+    for ak, func, arg in reqs:
+        if func == "count_star":
+            plan.append((ak, "count", star, None, None))
+            continue
+        if func == "dcount":
+            # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
+            # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
+            plan.append((ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None))
+            continue
+        ck = arg.key()
+        dtype, is_f = arg_types[ck]
+        if func == "count_if":
+            # the predicate mask (NULL counts as false) summed as int64; never NULL, so no count word
+            plan.append((ak, "cif", slot(("cif", ck), _MV_I64, _MA_ADD_U64), None, "long"))
+            continue
+        cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
+        if func == "count":
+            plan.append((ak, "count", cnt, None, None))
+        elif func in _VARIANCE:
+            # (n, Σx, M2) of the argument: the count and sum words AVG of the same argument uses, and one M2 word
+            # in a line only window_ring.hip combines (MA_M2); agg_multi leaves it at 0.0 (value kind -1) and
+            # win_m2_kernel fills it in the pane's second pass
+            if dtype not in ("byte", "short", "int", "long", "double", "float"):
+                raise Ineligible(f"{func} type")
+            sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
+            m2 = slot(("m2", ck), -1, _MA_M2)
+            m2_of[m2] = (cnt, sm)
+            plan.append((ak, func, m2, cnt, "double"))
+        elif func in ("bmin", "bmax"):
+            # bool_and / bool_or: MIN / MAX of the argument as int64, read back as "!= 0"
+            kind = _MV_I64 | (_MV_NOT if func == "bmin" else 0)
+            value_only.add(ak)
+            plan.append((ak, "i64", slot((func[1:], ck), kind, _MA_MAX), cnt, "boolean"))
+        elif func == "avg":
+            plan.append((ak, "avg", slot(("sumf", ck), _MV_F64, _MA_ADD_F64), cnt, "double"))
+        elif func == "sum":
+            if dtype not in ("byte", "short", "int", "long", "double", "float"):
+                raise Ineligible("sum type")
+            plan.append((ak, "sum", slot(("sum", ck), _MV_F64 if is_f else _MV_I64,
+                                         _MA_ADD_F64 if is_f else _MA_ADD_U64), cnt, "double" if is_f else "long"))
+        else:
+            kind = (_MV_F64_ORD if is_f else _MV_I64) | (_MV_NOT if func == "min" else 0)
+            plan.append((ak, "f64" if is_f else "i64", slot((func, ck), kind, _MA_MAX), cnt, dtype))
+    order, line_ops = [], []
+    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2):
+        mine = [i for i, sl in enumerate(slots) if sl[2] == op]
+        for k in range(0, len(mine), 8):
+            chunk = mine[k:k + 8]
+            line_ops.append(op)
+            order.extend(chunk + [None] * (8 - len(chunk)))
+    if len(order) > 64 or len(plan) > 64:
+        raise Ineligible("too many aggregates")
+    where = {i: pos for pos, i in enumerate(order) if i is not None}
+    nslots = len(order)
+    while nslots and order[nslots - 1] is None:
+        nslots -= 1
+    fin = []
+    for ak, kind, s, c, dt in plan:
+        if kind == "count":
+            fin.append((_F_COUNT, where[s], -1))
+        elif kind == "cif":
+            fin.append((_F_I64, where[s], -1))
+        elif kind in _VARIANCE:
+            fin.append((_VARIANCE[kind], where[s], where[c]))
+        elif kind == "avg":
+            fin.append((_F_AVG, where[s], where[c]))
+        elif kind == "sum":
+            fin.append((_F_F64 if dt == "double" else _F_I64, where[s], where[c]))
+        else:
+            k = (_F_F64_ORD if kind == "f64" else _F_I64) | (_F_NOT if slots[s][1] & _MV_NOT else 0)
+            fin.append((k, where[s], where[c]))
+    # partial states per aggregate (distagg._partials' suffixes): "cnt" a count, "v" the SUM / MIN / MAX value,
+    # "s" AVG's and the variance family's raw double sum, "m2" the centred sum of squares
+    pfin = {}
+    for j, (ak, kind, s, c, dt) in enumerate(plan):
+        if kind == "count":
+            pfin[ak] = {"cnt": (_F_COUNT, where[s], -1)}
+        elif kind == "cif":
+            pfin[ak] = {"cnt": (_F_I64, where[s], -1)}
+        elif kind == "avg":
+            pfin[ak] = {"s": (_F_F64, where[s], where[c]), "cnt": (_F_COUNT, where[c], -1)}
+        elif kind in _VARIANCE:
+            pfin[ak] = {"s": (_F_F64, where[m2_of[s][1]], where[c]), "m2": (_F_F64, where[s], where[c]),
+                        "cnt": (_F_COUNT, where[c], -1)}
+        elif ak in value_only:
+            pfin[ak] = {"v": fin[j]}
+        else:
+            pfin[ak] = {"v": fin[j], "cnt": (_F_COUNT, where[c], -1)}
+    stride = 8 * len(line_ops)
+    # per M2 word: its argument's count word | sum word << 16 (win_combine_kernel); the same three words per
+    # variance argument for win_m2_kernel
+    m2desc = [0] * stride
+    m2args = []
+    for m2, (c, sm) in m2_of.items():
+        m2desc[where[m2]] = where[c] | where[sm] << 16
+        m2args.append((slots[m2][0][1], where[c], where[sm], where[m2]))
+    dcount_word = {key[1]: where[i] for i, (key, _k, _o) in enumerate(slots) if key[0] == "dcount"}
+    return dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
+                count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word)
 
 
 class PairState:
@@ -343,6 +512,7 @@ class DenseWindow:
         self.NB = ring_slots // BLOCK + 4              # block slots after the pane and scratch slots
         self.blocks: Dict[int, tuple] = {}             # block id → (member entry ids, block slot, entries)
         self.layout = None              # built from the first pane's evaluated argument types
+        self.m2desc_t = self.m2desc_dev = None  # with variance arguments: win_combine_kernel's M2 descriptor
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
         self.free = list(range(ring_slots))    # free pane slots (a heap: the lowest is taken first)
         self.disabled = False
@@ -419,89 +589,23 @@ class DenseWindow:
             self.keys, self.dictcols = self._alloc_keys(kinds, self.gcap)
         except torch.cuda.OutOfMemoryError:
             raise Ineligible("memory") from None
-        # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
-        slots, keyed = [], {}
-
-        def slot(key, kind, op):
-            s = keyed.get(key)
-            if s is None:
-                s = keyed[key] = len(slots)
-                slots.append((key, kind, op))
-            return s
-
-        star = slot(("count", None), _MV_COUNT, _MA_ADD_F64)
-        plan = []
-        for ak, func, arg in self.reqs:
-            if func == "count_star":
-                plan.append((ak, "count", star, None, None))
-                continue
-            if func == "dcount":
-                # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
-                # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
-                plan.append((ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None))
-                continue
-            col = args[arg.key()]
-            ck = arg.key()
-            cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
-            if func == "count":
-                plan.append((ak, "count", cnt, None, None))
-                continue
-            is_f = col.data.dtype == torch.float64
-            if func == "avg":
-                plan.append((ak, "avg", slot(("sumf", ck), _MV_F64, _MA_ADD_F64), cnt, "double"))
-            elif func == "sum":
-                if col.dtype not in ("byte", "short", "int", "long", "double", "float"):
-                    raise Ineligible("sum type")
-                plan.append((ak, "sum", slot(("sum", ck), _MV_F64 if is_f else _MV_I64,
-                                             _MA_ADD_F64 if is_f else _MA_ADD_U64), cnt,
-                             "double" if is_f else "long"))
-            else:
-                kind = (_MV_F64_ORD if is_f else _MV_I64) | (_MV_NOT if func == "min" else 0)
-                plan.append((ak, "f64" if is_f else "i64", slot((func, ck), kind, _MA_MAX), cnt, col.dtype))
-        order, line_ops = [], []
-        for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX):
-            mine = [i for i, sl in enumerate(slots) if sl[2] == op]
-            for k in range(0, len(mine), 8):
-                chunk = mine[k:k + 8]
-                line_ops.append(op)
-                order.extend(chunk + [None] * (8 - len(chunk)))
-        if len(order) > 64 or len(plan) > 64:
-            raise Ineligible("too many aggregates")
-        where = {i: pos for pos, i in enumerate(order) if i is not None}
-        nslots = len(order)
-        while nslots and order[nslots - 1] is None:
-            nslots -= 1
-        fin = []
-        for ak, kind, s, c, dt in plan:
-            if kind == "count":
-                fin.append((_F_COUNT, where[s], -1))
-            elif kind == "avg":
-                fin.append((_F_AVG, where[s], where[c]))
-            elif kind == "sum":
-                fin.append((_F_F64 if dt == "double" else _F_I64, where[s], where[c]))
-            else:
-                k = (_F_F64_ORD if kind == "f64" else _F_I64) | (_F_NOT if slots[s][1] & _MV_NOT else 0)
-                fin.append((k, where[s], where[c]))
-        self.stride = 8 * len(line_ops)
-        # partial states per aggregate (distagg._partials' suffixes): "cnt" a count, "v" the SUM / MIN / MAX value,
-        # "s" AVG's raw double sum
-        pfin = {}
-        for ak, kind, s, c, dt in plan:
-            if kind == "count":
-                pfin[ak] = {"cnt": (_F_COUNT, where[s], -1)}
-            elif kind == "avg":
-                pfin[ak] = {"s": (_F_F64, where[s], where[c]), "cnt": (_F_COUNT, where[c], -1)}
-            else:
-                pfin[ak] = {"v": fin[len(pfin)], "cnt": (_F_COUNT, where[c], -1)}
-        self.stride = 8 * len(line_ops)
-        self.layout = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, plan=plan,
-                           count_word=where[star], fin=fin, pfin=pfin, pspec_of=self._partial_spec)
-        self.line_ops_t = torch.tensor(line_ops, dtype=torch.int32)
-        self.line_ops_dev = self.line_ops_t.to(self.device)
+        L = plan_layout(self.reqs, {k: (c.dtype, c.data.dtype == torch.float64) for k, c in args.items()})
+        L["pspec_of"] = self._partial_spec
+        self.stride = L["stride"]
+        self.layout = L
+        # agg_multi (host ``line_ops_t``) sees an M2 line as an f64 add line of unused slots, so every pane starts
+        # its M2 words at 0.0; the ring kernels (``line_ops_dev``) see MA_M2
+        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op == _MA_M2 else op for op in L["line_ops"]],
+                                       dtype=torch.int32)
+        self.line_ops_dev = torch.tensor(L["line_ops"], dtype=torch.int32).to(self.device)
+        self.m2desc_t = self.m2desc_dev = None
+        if L["m2args"]:
+            self.m2desc_t = torch.tensor(L["m2desc"], dtype=torch.int32)
+            self.m2desc_dev = self.m2desc_t.to(self.device)
         try:
             self.ring, self.acc, self.keep, self.out_idx = self._alloc_ring(self.gcap)
             for ps in self.pairs:
-                ps.build(dargs[ps.arg_key], where[keyed[("dcount", ps.arg_key)]])
+                ps.build(dargs[ps.arg_key], L["dcount_word"][ps.arg_key])
         except torch.cuda.OutOfMemoryError:
             self.layout = None
             raise Ineligible("memory") from None
@@ -657,18 +761,24 @@ class DenseWindow:
         N.call("dxa_win_insert_fused", ctypes.addressof(kc), ctypes.addressof(self.dictcols), N.ptr(keep),
                N.ptr(self.htab), self.hcap, N.ptr(self.gid_of_slot), N.ptr(self.scal), N.ptr(gid), st)
         spec, hold = [], [gid, keep, kc]
+        xs = {}                         # variance arguments: the (float64 values, validity) their sum slot reads
         for i in L["order"][:L["nslots"]]:
             if i is None:
                 spec += [0, 0, -1]
                 continue
             key, kind, _op = L["slots"][i]
-            if key[0] == "dcount":
+            if key[0] in ("dcount", "m2"):         # filled after agg_multi: by the distinct fold / win_m2_kernel
                 spec += [0, 0, -1]
                 continue
             if key[1] is None:
                 spec += [0, 0, kind]
                 continue
             c = args[key[1]]
+            if key[0] == "cif":                    # count_if: the predicate mask as int64, NULL → 0
+                d = predicate_mask(c).to(torch.int64).contiguous()
+                hold.append(d)
+                spec += [d.data_ptr(), 0, kind]
+                continue
             v = N.u8(c.valid)
             if v is not None:
                 v = v.contiguous()
@@ -683,11 +793,23 @@ class DenseWindow:
                 d = d.to(torch.int64)
             d = d.contiguous()
             hold += [d, v]
+            if key[0] == "sumf":
+                xs[key[1]] = (d, v)
             spec += [d.data_ptr(), 0 if v is None else v.data_ptr(), kind]
         spec_t = torch.tensor(spec, dtype=torch.int64)
         ring_ptr = self.ring[slot_idx].data_ptr()
         N.call("dxa_aggregate_multi", N.ptr(gid), n, self.gcap + 1, L["nslots"], spec_t.data_ptr(),
                len(L["line_ops"]), self.line_ops_t.data_ptr(), ring_ptr, st)
+        if L["m2args"] and n > 0:
+            # the pane's second pass: the slot's counts and sums are complete, so every row's distance from its
+            # group's mean goes into the M2 words (window_ring.hip win_m2_kernel), all variance arguments at once
+            m = _M2Args()
+            for k, (ck, cw, sw, mw) in enumerate(L["m2args"]):
+                d, v = xs[ck]
+                m.a[k] = _M2Arg(d.data_ptr(), 0 if v is None else v.data_ptr(), cw, sw, mw, 0)
+            m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
+            m.gcap, m.stride, m.nargs = self.gcap, self.stride, len(L["m2args"])
+            N.call("dxa_win_m2", ctypes.addressof(m), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
@@ -715,8 +837,13 @@ class DenseWindow:
         member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
         slots_dev = self._dev_slots(member_slots)
         st = N.stream_handle(self.device)
-        N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
-               len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), st)
+        if self.m2desc_dev is not None:
+            N.call("dxa_win_combine_block_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
+                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.ptr(self.m2desc_dev),
+                   self.m2desc_t.data_ptr(), st)
+        else:
+            N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
+                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), st)
         for ps in self.pairs:       # the members' presence rows ORed into the same block slot of the presence ring
             N.call("dxa_win_pair_or_block", N.ptr(ps.pres), ps.pitch, N.ptr(slots_dev), len(member_slots), dst, st)
         self.blocks[bid] = (members, dst, list(mem))
@@ -736,6 +863,7 @@ class DenseWindow:
         slots_dev = self._dev_slots(slots)
         fin = L["pspec_of"](partial_proto) if partial_proto is not None else L["fin"]
         e, bufs = self._emit_args(fin)
+        folds = None
         if self.pairs:
             # the same launches with one distinct fold per pair state between the combine and the keep pass
             folds = _PairFolds()
@@ -743,6 +871,14 @@ class DenseWindow:
                 folds.p[k] = _PairFold(ps.pres.data_ptr(), ps.pitch, ps.keys[0][2].data_ptr(), ps.scal_ptr, ps.pcap,
                                        ps.word)
             folds.n = len(self.pairs)
+        if self.m2desc_dev is not None:
+            # a layout with M2 lines: the combine that knows Chan's update, with or without distinct folds
+            N.call("dxa_win_answer_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
+                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
+                   0 if folds is None else ctypes.addressof(folds), N.ptr(self.m2desc_dev),
+                   self.m2desc_t.data_ptr(), st)
+        elif self.pairs:
             N.call("dxa_win_answer_distinct", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
                    N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
                    N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
@@ -785,7 +921,7 @@ class DenseWindow:
             # no row passed the WHERE anywhere in the window: Spark's one row — counts 0, everything else NULL
             finals = {}
             for ak, kind, s, c, dt in L["plan"]:
-                if kind == "count":
+                if kind in ("count", "cif"):
                     finals[ak] = PrimColumn("long", torch.zeros(1, dtype=torch.int64, device=self.device))
                 else:
                     td = torch.float64 if kind in ("avg", "f64") or dt == "double" else \
@@ -813,9 +949,9 @@ class DenseWindow:
             return self._partials(cols, out_keys, nout, *partial_proto)
         finals = {}
         for (ak, kind, s, c, dt), (v, ok) in zip(L["plan"], cols):
-            if kind == "count":
+            if kind in ("count", "cif"):
                 finals[ak] = PrimColumn("long", v)
-            elif kind == "avg":
+            elif kind == "avg" or kind in _VARIANCE:
                 finals[ak] = PrimColumn("double", v.view(torch.float64), ok)
             elif kind == "sum":
                 finals[ak] = PrimColumn(dt, v.view(torch.float64) if dt == "double" else v, ok)

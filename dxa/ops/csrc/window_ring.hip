@@ -35,6 +35,10 @@ constexpr int kMaxKeyCols = 16;
 constexpr int kKeyWidth = 48;            // bytes of a string key kept in the dictionary
 enum : int32_t { KC_I64 = 0, KC_F64 = 1, KC_STR = 2 };
 enum : int32_t { MA_ADD_U64 = 0, MA_ADD_F64 = 1, MA_MAX_I64 = 2 };
+// A combine op of this file only: the word is a group's centred sum of squares M2 = Σ (x − mean)² about the mean of
+// the slot's own rows.  agg_multi sees such a line as MA_ADD_F64 with unused slots (every pane starts it at 0.0),
+// win_m2_kernel fills it, and slots are combined with Chan et al.'s update (win_combine_kernel).
+enum : int32_t { MA_M2 = 3 };
 
 // same layout as hash_groupby.hip's KeyCols (built by dxa/ops/hashing.py key_cols)
 struct KeyCol {
@@ -81,13 +85,20 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
 // the groups the dictionary holds: the rows above them are the identity in every member (no row has been
 // accumulated there), so they are written as the identity without a read and the cost follows the groups in use,
 // not the capacity.  (A template parameter, so the per-batch combine keeps its wave-uniform slot loop.)
-template <bool kBlock>
+// ``kM2``: the layout has MA_M2 lines and ``m2desc`` [stride] names, for each M2 word, the row's count word (low 16
+// bits) and sum word (high 16 bits) of the same argument.  An M2 word combines as
+//   M2 = Σ_s [ M2_s + n_s (sum_s / n_s − mean)² ],  mean = Σ sum_s / Σ n_s,  over the slots with n_s > 0
+// (the multi-way form of Chan's update: exact algebra, every term centred), so a block slot holds a valid
+// (n, sum, M2) triple about the block's mean and blocks and loose panes combine by the same formula.  Without kM2
+// the branch is compiled out (dxa_win_live runs that form over any layout: it reads the count word only).
+template <bool kBlock, bool kM2>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
                                                           int32_t nslots_in, int32_t stride,
                                                           const int32_t* __restrict__ line_op,
                                                           const int32_t* __restrict__ scal, int32_t gcap,
-                                                          int32_t fixed_rows, unsigned long long* __restrict__ out) {
+                                                          int32_t fixed_rows, unsigned long long* __restrict__ out,
+                                                          const int32_t* __restrict__ m2desc) {
   int32_t ng = scal[0];
   if (ng > gcap) ng = gcap;
   const int64_t held = (int64_t)ng * stride;
@@ -105,6 +116,25 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
       unsigned long long acc = 0;
       for (int s = 0; s < nslots; ++s) acc += ring[(int64_t)slots[s] * slot_words + idx];
       out[idx] = acc;
+    } else if (kM2 && op == MA_M2) {
+      const int32_t dsc = m2desc[w];
+      const int64_t ci = idx - w + (dsc & 0xffff), si = idx - w + (dsc >> 16);
+      double n = 0.0, sum = 0.0;
+      for (int s = 0; s < nslots; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        n += __longlong_as_double((long long)ring[base + ci]);
+        sum += __longlong_as_double((long long)ring[base + si]);
+      }
+      const double mean = sum / (n > 0.0 ? n : 1.0);
+      double acc = 0.0;
+      for (int s = 0; s < nslots; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        const double ns = __longlong_as_double((long long)ring[base + ci]);
+        if (ns == 0.0) continue;
+        const double d = __longlong_as_double((long long)ring[base + si]) / ns - mean;
+        acc += __longlong_as_double((long long)ring[base + idx]) + ns * d * d;
+      }
+      out[idx] = (unsigned long long)__double_as_longlong(acc);
     } else {
       long long acc = (long long)0x8000000000000000ull;
       for (int s = 0; s < nslots; ++s) {
@@ -158,6 +188,61 @@ __global__ __launch_bounds__(256) void win_compact_kernel(const uint8_t* __restr
       if (g < ng && keep[g]) out_idx[pos++] = g;
     }
     base += part[255];
+    __syncthreads();
+  }
+}
+
+// 2b. the second pass of a pane's accumulation, for the variance family: agg_multi has finished the slot's count and
+// sum words, so every row's group mean is known and each row with a valid argument adds (x − sum_g / n_g)² into the
+// group's M2 word — the centred form; Σx² − (Σx)²/n would cancel catastrophically at offset values.  Rows of the dump
+// row (WHERE-filtered or dictionary-full, gid == gcap) are skipped: nobody reads its M2 and they would all hit one
+// address.  A window with a handful of groups puts every row of a pane on a handful of words, and every adder on one
+// row runs an order of magnitude below the float-atomic rate, so groups with ids below kM2LdsGroups are summed in
+// LDS (f64 LDS adds) and flushed with one global add per touched group and workgroup; ids at or above the bound go
+// straight to global adds, which such a dictionary spreads over many rows.  The choice is made per row here — the
+// host's group count is a batch stale — so both halves are always correct.  One launch covers all of a statement's
+// variance arguments, one after the other through the same LDS array.
+constexpr int kMaxM2Args = 8;
+constexpr int kM2LdsGroups = 1024;
+struct M2Arg {
+  const double* x;
+  const uint8_t* valid;
+  int32_t cnt;             // words of the slot row: the argument's count, sum and M2
+  int32_t sum;
+  int32_t m2;
+  int32_t pad;
+};
+struct M2Args {
+  M2Arg a[kMaxM2Args];
+  const int32_t* gid;
+  double* row;             // the ring slot: [gcap + 1][stride]
+  int64_t n;
+  int32_t gcap;
+  int32_t stride;
+  int32_t nargs;
+  int32_t pad;
+};
+
+__global__ __launch_bounds__(256) void win_m2_kernel(const M2Args m) {
+  __shared__ double part[kM2LdsGroups];
+  const int32_t lds_groups = m.gcap < kM2LdsGroups ? m.gcap : kM2LdsGroups;
+  for (int k = 0; k < m.nargs; ++k) {
+    const M2Arg a = m.a[k];
+    for (int g = threadIdx.x; g < kM2LdsGroups; g += blockDim.x) part[g] = 0.0;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m.n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int32_t g = m.gid[i];
+      if (g < 0 || g >= m.gcap || (a.valid && !a.valid[i])) continue;
+      double* r = m.row + (int64_t)g * m.stride;
+      const double d = a.x[i] - r[a.sum] / r[a.cnt];      // the row itself was counted: n_g ≥ 1
+      if (g < kM2LdsGroups) atomicAdd(&part[g], d * d);
+      else atomicAdd(r + a.m2, d * d);
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < lds_groups; g += blockDim.x) {
+      const double v = part[g];
+      if (v != 0.0) atomicAdd(m.row + (int64_t)g * m.stride + a.m2, v);
+    }
     __syncthreads();
   }
 }
@@ -290,7 +375,8 @@ __global__ void win_insert_kernel(const KeyCols a, DictCols d, const uint8_t* __
 // finished from the combined accumulator row (the kinds of hash_groupby.hip agg_finish_kernel).  Outputs are
 // [gcap]-strided; the host slices the first ``kept`` entries after its one read.
 constexpr int kMaxEmit = 64;
-enum : int { F_COUNT = 0, F_I64 = 1, F_F64 = 2, F_AVG = 3, F_F64_ORD = 4, F_NOT = 8 };
+enum : int { F_COUNT = 0, F_I64 = 1, F_F64 = 2, F_AVG = 3, F_F64_ORD = 4, F_VAR_SAMP = 5, F_VAR_POP = 6, F_NOT = 8,
+             F_SQRT = 16 };
 struct EmitArgs {
   const long long* acc;
   int32_t stride;
@@ -333,6 +419,18 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
         case F_COUNT: o = (long long)__longlong_as_double(v); break;
         case F_AVG: o = __double_as_longlong(__longlong_as_double(v) / (c > 1.0 ? c : 1.0)); break;
         case F_F64_ORD: o = v < 0 ? (v ^ 0x7fffffffffffffffll) : v; break;
+        case F_VAR_SAMP:
+        case F_VAR_POP: {
+          // pos = the M2 word, cnt = the count word n: M2 / (n − 1) or M2 / n; Spark 2.4's sample statistic of
+          // one row is NaN (n = 0 is NULL by the validity rule below)
+          const bool samp = (k & 7) == F_VAR_SAMP;
+          const double den = samp ? c - 1.0 : c;
+          double r = __longlong_as_double(v) / (den > 0.0 ? den : 1.0);
+          if (samp && c == 1.0) r = __longlong_as_double(0x7ff8000000000000ll);
+          if (k & F_SQRT) r = sqrt(r);
+          o = __double_as_longlong(r);
+          break;
+        }
         default: o = v; break;
       }
       e.dst[(int64_t)r * e.gcap + p] = o;
@@ -558,9 +656,9 @@ DXA_API int dxa_win_combine(const void* ring, int32_t gcap, int32_t stride, cons
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL(win_combine_kernel<false>, dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+  hipLaunchKernelGGL((win_combine_kernel<false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
                      s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc);
+                     (unsigned long long*)acc, (const int32_t*)nullptr);
   hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
                      (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
   hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
@@ -574,9 +672,9 @@ DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, cons
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL(win_combine_kernel<true>, dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
+  hipLaunchKernelGGL((win_combine_kernel<true, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
                      dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, gcap + 1, r + (int64_t)dst * slot_words);
+                     gcap, gcap + 1, r + (int64_t)dst * slot_words, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -715,9 +813,83 @@ DXA_API int dxa_win_answer_distinct(const void* ring, int32_t gcap, int32_t stri
       return (int)hipErrorInvalidValue;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL(win_combine_kernel<false>, dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+  hipLaunchKernelGGL((win_combine_kernel<false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
                      s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc);
+                     (unsigned long long*)acc, (const int32_t*)nullptr);
+  for (int k = 0; k < pf.n; ++k)
+    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
+                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
+  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
+  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *(const EmitArgs*)emit,
+                     *(const DictCols*)dictcols);
+  return (int)hipGetLastError();
+}
+
+// ---- STDDEV / VARIANCE: entry points -----------------------------------------------------------------------------
+
+DXA_API int dxa_win_m2_size() { return (int)sizeof(M2Args); }
+
+// ids below this are summed in LDS by win_m2_kernel, the others add straight to global memory
+DXA_API int dxa_win_m2_lds_groups() { return kM2LdsGroups; }
+
+// a pane's M2 words, on the same stream right after dxa_aggregate_multi filled the slot (win_m2_kernel)
+DXA_API int dxa_win_m2(const void* args, void* st) {
+  const M2Args& m = *(const M2Args*)args;
+  if (m.nargs < 0 || m.nargs > kMaxM2Args || m.gcap < 0 || m.stride <= 0) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < m.nargs; ++k) {
+    const M2Arg& a = m.a[k];
+    if (a.cnt < 0 || a.cnt >= m.stride || a.sum < 0 || a.sum >= m.stride || a.m2 < 0 || a.m2 >= m.stride || !a.x)
+      return (int)hipErrorInvalidValue;
+  }
+  if (m.n <= 0 || m.nargs == 0) return 0;
+  // 8 rows per lane amortise a workgroup's LDS clear and flush; at most two workgroups per CU's worth of adders
+  hipLaunchKernelGGL(win_m2_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
+  return (int)hipGetLastError();
+}
+
+static bool m2desc_ok(const int32_t* host_desc, int32_t stride) {
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d < 0 || (d & 0xffff) >= stride || (d >> 16) >= stride) return false;
+  }
+  return true;
+}
+
+// dxa_win_combine_block for a layout with M2 lines.  ``m2desc`` [stride] on the device (win_combine_kernel),
+// ``m2desc_host`` the same words for the bounds check.
+DXA_API int dxa_win_combine_block_m2(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                                     const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
+                                     const int32_t* m2desc_host, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride)) return (int)hipErrorInvalidValue;
+  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+  unsigned long long* r = (unsigned long long*)ring;
+  hipLaunchKernelGGL((win_combine_kernel<true, true>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
+                     dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
+                     gcap, gcap + 1, r + (int64_t)dst * slot_words, m2desc);
+  return (int)hipGetLastError();
+}
+
+// dxa_win_answer / dxa_win_answer_distinct for a layout with M2 lines (``folds`` may be null: no distinct counts)
+DXA_API int dxa_win_answer_m2(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                              const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
+                              int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
+                              const int32_t* m2desc, const int32_t* m2desc_host, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride)) return (int)hipErrorInvalidValue;
+  PairFolds none{};
+  const PairFolds& pf = folds ? *(const PairFolds*)folds : none;
+  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < pf.n; ++k)
+    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
+      return (int)hipErrorInvalidValue;
+  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+  hipMemsetAsync(scal + 2, 0, 4, s);
+  hipLaunchKernelGGL((win_combine_kernel<false, true>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
+                     dim3(256), 0, s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal,
+                     gcap, 0, (unsigned long long*)acc, m2desc);
   for (int k = 0; k < pf.n; ++k)
     hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
                        dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);

@@ -319,6 +319,10 @@ _RENUMBER_MAX = 4096          # hash_groupby.hip kRenumberMax: one-workgroup bit
 _RENUMBER_BITMAP_ROWS = 8192 * 64   # kBitmapRows: first-row bitmap renumbering (any number of groups)
 _MV_COUNT, _MV_I64, _MV_F64, _MV_F64_ORD, _MV_NOT = 0, 1, 2, 3, 4
 _F_COUNT, _F_I64, _F_F64, _F_AVG, _F_F64_ORD, _F_NOT = 0, 1, 2, 3, 4, 8       # hash_groupby.hip agg_finish_kernel
+# window_ring.hip only (win_combine_kernel / win_emit_kernel): the M2 combine op of a variance argument's line, and
+# the finishing kinds M2 / (n - 1), M2 / n with the flag "then the square root"
+_MA_M2 = 3
+_F_VAR_SAMP, _F_VAR_POP, _F_SQRT = 5, 6, 16
 _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096
