@@ -5,6 +5,12 @@ sum of squares …).  Phase 2: route each partial group to ``hash(keys) % world`
 owner and *merge* the partial states.  Aggregates that have no mergeable partial state (COUNT DISTINCT,
 collect_list/set, user UDAFs) fall back to shuffling the input rows by key hash and aggregating once on the owner —
 still one exchange, just a bigger one.
+
+The central-moment aggregates are mergeable too: the variance family keeps (s, m2, cnt) per partial group, skewness
+(s, m2, m3, cnt), kurtosis (s, m2, m3, m4, cnt), covar_pop / covar_samp (sx, sy, cxy, cnt) and corr (sx, sy, m2x, m2y,
+cxy, cnt) — every m* / cxy centred on the partial group's own means, a pair's states taken over the rows where both
+arguments are non-null — merged with the multi-way form of Chan's update (``_chan_merge``) and finished by Spark 2.4's
+rules (``_finish``).  The same states come out of the dense window ring (``window_dense.dense_partials``).
 """
 from __future__ import annotations
 
@@ -23,7 +29,11 @@ from .decimal import is_decimal
 
 DECOMPOSABLE = {"count", "sum", "min", "max", "avg", "mean", "first", "last", "first_value", "last_value",
                 "stddev", "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "std", "count_if",
-                "bool_and", "bool_or", "every", "any", "some"}
+                "bool_and", "bool_or", "every", "any", "some", "skewness", "kurtosis", "covar_pop", "covar_samp",
+                "corr"}
+_PAIRED = ("covar_pop", "covar_samp", "corr")
+# merge ops of the centred states: summed over the parts, then completed by ``_chan_merge``
+_CENTRED = ("m2", "m3", "m4", "cxy")
 
 
 def decomposable(calls: Dict, ctx) -> bool:
@@ -40,6 +50,20 @@ def _partials(call: A.Call, scope, ctx) -> List[Tuple[str, Optional[PrimColumn],
     name = call.name
     if call.star or (name == "count" and not call.args):
         return [("cnt", None, "count_star", "sum")]
+    if name in _PAIRED:
+        # (Σx, Σy, Cxy, n) over the rows where both arguments are non-null; corr adds both M2s over the same rows
+        if len(call.args) != 2:
+            raise ValueError(f"{name} takes two arguments")
+        x, y = (_as_double(evaluate(a, scope, ctx)) for a in call.args)
+        both = x.valid_mask() & y.valid_mask()
+        x, y = PrimColumn("double", x.data, both), PrimColumn("double", y.data, both)
+        m2 = [("m2x", x, "m2", "m2"), ("m2y", y, "m2", "m2")] if name == "corr" else []
+        return [("sx", x, "sum", "sum"), ("sy", y, "sum", "sum"), *m2, ("cxy", (x, y), "cxy", "cxy"),
+                ("cnt", x, "count", "sum")]
+    if name in ("skewness", "kurtosis"):
+        x = _as_double(evaluate(call.args[0], scope, ctx))
+        m4 = [("m4", x, "m4", "m4")] if name == "kurtosis" else []
+        return [("s", x, "sum", "sum"), ("m2", x, "m2", "m2"), ("m3", x, "m3", "m3"), *m4, ("cnt", x, "count", "sum")]
     arg = materialize(evaluate(call.args[0], scope, ctx))
     if isinstance(arg, ConstColumn):
         arg = arg.materialize()
@@ -72,8 +96,57 @@ def _partials(call: A.Call, scope, ctx) -> List[Tuple[str, Optional[PrimColumn],
     return [("s", x, "sum", "sum"), ("m2", x, "m2", "m2"), ("cnt", arg, "count", "sum")]
 
 
+def _as_double(c) -> PrimColumn:
+    c = materialize(c)
+    if isinstance(c, ConstColumn):
+        c = c.materialize()
+    if is_decimal(c.dtype):
+        c = Dec.to_double(c)
+    return PrimColumn("double", c.data.to(torch.float64), c.valid)
+
+
+def _centred_sum(groups, func: str, arg, n: int) -> PrimColumn:
+    """A local partial's Σ d³ ("m3"), Σ d⁴ ("m4") or Σ d_x d_y ("cxy") per group about the group's own means, as a
+    tensor program (two passes, as ``query._moments``): the fallback and wire format, not the hot path."""
+    cols = list(arg) if isinstance(arg, tuple) else [arg]
+    ng, dev = groups.ngroups, cols[0].data.device
+    ok = cols[0].valid_mask()
+    idx = torch.nonzero(ok).flatten()
+    gid = groups.gid.to(torch.int64)[idx] if n else idx
+
+    def gsum(v):
+        return torch.zeros(ng, dtype=torch.float64, device=dev).index_add_(0, gid, v)
+    cnt = gsum(torch.ones(idx.shape[0], dtype=torch.float64, device=dev))
+    d = []
+    for c in cols:
+        v = c.data[idx]
+        d.append(v - (gsum(v) / cnt.clamp(min=1))[gid])
+    out = gsum(d[0] * d[1]) if func == "cxy" else gsum(d[0] * d[0] * d[0] * (d[0] if func == "m4" else 1.0))
+    return PrimColumn("double", out, cnt > 0)
+
+
 def _finish(call: A.Call, merged: Dict[str, PrimColumn]) -> PrimColumn:
     name = call.name
+    if "cxy" in merged or "m3" in merged:
+        # Spark 2.4's Covariance / Corr / CentralMomentAgg, as ``query._moments``: NULL for no rows, NaN where
+        # Spark divides by zero
+        c = merged["cnt"].data.to(torch.float64)
+        nan = torch.full_like(c, float("nan"))
+        one = torch.ones_like(c)
+        if name == "covar_pop":
+            out = merged["cxy"].data / c.clamp(min=1)
+        elif name == "covar_samp":
+            out = torch.where(c > 1, merged["cxy"].data / (c - 1).clamp(min=1), nan)
+        elif name == "corr":
+            p = merged["m2x"].data * merged["m2y"].data
+            out = torch.where(p > 0, merged["cxy"].data / torch.where(p > 0, p, one).sqrt(), nan)
+        else:
+            m2 = merged["m2"].data
+            safe = torch.where(m2 > 0, m2, one)
+            r = c.sqrt() * merged["m3"].data / safe ** 1.5 if name == "skewness" else \
+                c * merged["m4"].data / (safe * safe) - 3.0
+            out = torch.where(m2 > 0, r, nan)
+        return PrimColumn("double", out, c > 0)
     if "v" in merged:
         v = merged["v"]
         if name in ("bool_and", "every", "bool_or", "any", "some"):
@@ -186,7 +259,9 @@ def local_partials(gexprs, keys, aggs: Dict, scope, ctx):
             plan[ak].append((nm, suffix, op))
             names.append(nm)
             reqs.append((arg, func))
-    cols.extend(G.aggregate_many(groups, reqs, n))
+    # the higher centred sums are tensor programs of their own; everything else is evaluated together
+    fused = iter(G.aggregate_many(groups, [r for r in reqs if r[1] not in ("m3", "m4", "cxy")], n))
+    cols.extend(_centred_sum(groups, f, a, n) if f in ("m3", "m4", "cxy") else next(fused) for a, f in reqs)
     ng_local = groups.ngroups if (gexprs or n) else 0
     if not gexprs and n == 0:
         cols = [c.take(torch.empty(0, dtype=torch.int64, device=dev)) for c in cols]
@@ -253,33 +328,56 @@ def combine_partials(got: Table, plan, key_names: List[str], grouped: bool) -> T
 
 
 def _merge_op(op: str) -> str:
-    return "sum" if op == "m2" else op
+    return "sum" if op in _CENTRED else op
 
 
 def _chan_merge(g2, got: Table, entries, vals, m: int):
-    """Complete the M2 merges of the variance family: the partial M2s were summed; Chan et al.'s pairwise update
-    adds Σ n_i (mean_i − mean)² over the partials of each merged group (mean = Σ s_i / Σ n_i), which is exact
-    algebra for any number of partials and keeps every term centred."""
+    """Complete the merges of the centred states: the parts' M2 / M3 / M4 / Cxy were summed; the multi-way form of
+    Chan et al.'s update adds, over the parts i of each merged group with n_i > 0 and δ_i = s_i / n_i − Σ s / Σ n
+    (ε_i the same for y),
+
+        M2: Σ n_i δ_i²        M3: Σ [3 δ_i M2_i + n_i δ_i³]        M4: Σ [4 δ_i M3_i + 6 δ_i² M2_i + n_i δ_i⁴]
+        Cxy: Σ n_i δ_i ε_i
+
+    which is exact algebra for any number of parts, keeps every term centred and reads only the parts' own states
+    (from ``got``), never a merged one."""
     by_agg = {}
     for j, (ak, nm, suffix, _op) in enumerate(entries):
         by_agg.setdefault(ak, {})[suffix] = (j, nm)
     gid = g2.gid.to(torch.int64)
     for ak, parts in by_agg.items():
-        if "m2" not in parts:
+        if not any(sfx in parts for sfx in ("m2", "m2x", "cxy")):
             continue
-        jm, _ = parts["m2"]
-        js, ns = parts["s"]
         jc, nc = parts["cnt"]
         n_i = got.column(nc).data.to(torch.float64)
-        s_i = got.column(ns).data.to(torch.float64)
-        n = vals[jc].data.to(torch.float64)
-        mean = vals[js].data.to(torch.float64) / n.clamp(min=1)
-        mean_i = s_i / n_i.clamp(min=1)
-        d = mean_i - mean[gid]
-        corr = G.aggregate(g2, PrimColumn("double", torch.where(n_i > 0, n_i * d * d, torch.zeros_like(d))), "sum",
-                           m)
-        mv = vals[jm]
-        vals[jm] = PrimColumn("double", mv.data + corr.data, mv.valid)
+        n = vals[jc].data.to(torch.float64).clamp(min=1)
+        has = n_i > 0
+
+        def shift(suffix):
+            js, ns = parts[suffix]
+            return got.column(ns).data.to(torch.float64) / n_i.clamp(min=1) - (vals[js].data.to(torch.float64) / n)[gid]
+
+        def own(suffix):
+            return got.column(parts[suffix][1]).data.to(torch.float64)
+
+        def add(suffix, term):
+            j = parts[suffix][0]
+            extra = G.aggregate(g2, PrimColumn("double", torch.where(has, term, torch.zeros_like(term))), "sum", m)
+            vals[j] = PrimColumn("double", vals[j].data + extra.data, vals[j].valid)
+
+        if "cxy" in parts:
+            dx, dy = shift("sx"), shift("sy")
+            add("cxy", n_i * dx * dy)
+            if "m2x" in parts:
+                add("m2x", n_i * dx * dx)
+                add("m2y", n_i * dy * dy)
+            continue
+        d = shift("s")
+        add("m2", n_i * d * d)
+        if "m3" in parts:
+            add("m3", 3.0 * d * own("m2") + n_i * d * d * d)
+        if "m4" in parts:
+            add("m4", 4.0 * d * own("m3") + 6.0 * d * d * own("m2") + n_i * d * d * d * d)
     return vals
 
 

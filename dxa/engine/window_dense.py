@@ -16,8 +16,9 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
   synchronisation — and builds the output columns as views of the dictionary and the finished aggregates.
 
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over non-decimal numeric,
-boolean or timestamp arguments (and COUNT(DISTINCT x) and the variance family, below; count_if; bool_and / every,
-bool_or / any / some), with plain key columns, deterministic, on a GPU.  With N ranks each rank's window
+boolean or timestamp arguments (and COUNT(DISTINCT x), the variance family and corr / covar_pop / covar_samp /
+skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some), with plain key columns,
+deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
 exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
 reports a hash collision or an over-long string key — is answered by the paned path, which stays the reference
@@ -64,6 +65,24 @@ a block slot is again a valid triple and nothing is ever computed as Σx² − (
 argument has no such line and issues exactly the launches it issued before (``dxa_win_answer_m2`` /
 ``dxa_win_combine_block_m2`` sit beside the plain entry points as ``dxa_win_answer_distinct`` does).  With N ranks
 the partial states are ("s", "m2", "cnt"), the table ``distagg._partials`` builds.
+
+**CORR / COVAR_POP / COVAR_SAMP / SKEWNESS / KURTOSIS** (``_MOMENTS``; up to ``MAX_MOMENTS`` different arguments
+and pairs per statement, fallback reason "too many moment arguments") close the moment family.  skewness(x) /
+kurtosis(x) reuse x's count, sum and M2 words and add M3 = Σ (x − mean)³ (kurtosis also M4, whose combine reads M3).
+A pair (x, y) is keyed by both argument keys (``pair_keys``) and shared by corr, covar_pop and covar_samp of it: a
+count and two sums over the rows where both are non-null — the argument columns keep their data under the validity
+``x.valid & y.valid``, built once per pane in ``accumulate`` — a word Cxy = Σ (x − mean_x)(y − mean_y), and for corr
+two ordinary M2 words over the masked columns (the variance machinery, unchanged; they count towards
+``MAX_VARIANCE``).  M3, M4 and Cxy sit in lines of one more combine op (``MA_MOM`` = 4) that agg_multi sees as
+unused; ``momdesc`` names per word its kind and the words it reads (count, sum, M2 / sum of y, M3; 6 bits each).
+``win_mom_kernel`` fills them after the multi-aggregate (one sweep per argument or pair, all of its words at once),
+the combine merges slots with the multi-way shift formulas (window_ring.hip), and ``win_emit_kernel`` finishes them
+by Spark 2.4's rules (``fin`` entries of these kinds carry two more operand words).  A layout without one of these
+aggregates has no op-4 line, no ``momdesc`` and issues the launches it issued before (``dxa_win_answer_mom`` /
+``dxa_win_combine_block_mom`` are further siblings of the plain entry points).  The NaN rules test M2 > 0 on a
+rounded M2: equal values that are not exactly summable can give a huge number where Spark gives NaN
+(``query._moments`` has the same property).  With N ranks the partial states are those of ``distagg._partials``:
+("s", "m2", "m3"[, "m4"], "cnt") and ("sx", "sy"[, "m2x", "m2y"], "cxy", "cnt").
 """
 from __future__ import annotations
 
@@ -74,9 +93,10 @@ from typing import Dict, List, Optional
 import torch
 
 from ..ops import native as N
-from ..ops.groupby import (_F_AVG, _F_COUNT, _F_F64, _F_F64_ORD, _F_I64, _F_NOT, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP,
-                           _MA_ADD_F64, _MA_ADD_U64, _MA_M2, _MA_MAX, _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64,
-                           _MV_NOT)
+from ..ops.groupby import (_F_AVG, _F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP, _F_F64, _F_F64_ORD, _F_I64,
+                           _F_KURT, _F_NOT, _F_SKEW, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64,
+                           _MA_M2, _MA_MAX, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT, _MV_F64, _MV_F64_ORD,
+                           _MV_I64, _MV_NOT)
 from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
 from .decimal import is_decimal
@@ -89,6 +109,7 @@ DENSE_PAIRS = 1 << 16             # initial capacity of a COUNT(DISTINCT x) pair
 DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring is one byte per ring slot and pair)
 MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
 MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per statement (window_ring.hip kMaxM2Args)
+MAX_MOMENTS = 8                   # skewness / kurtosis arguments plus corr / covar pairs (window_ring.hip kMaxMomArgs)
 N.register_sigs({
     "dxa_win_pairfold_size": [],
     "dxa_win_pair_prep": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
@@ -106,12 +127,31 @@ N.register_sigs({
     "dxa_win_answer_m2": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
                           N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
 })
+N.register_sigs({
+    "dxa_win_mom_size": [],
+    "dxa_win_mom": [N.c_p, N.c_p],
+    "dxa_win_combine_block_mom": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p,
+                                  N.c_p, N.c_p],
+    "dxa_win_answer_mom": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
+                           N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
+})
 # the variance family → the finishing kind of its M2 word (window_ring.hip win_emit_kernel)
 _VARIANCE = {"stddev": _F_VAR_SAMP | _F_SQRT, "std": _F_VAR_SAMP | _F_SQRT, "stddev_samp": _F_VAR_SAMP | _F_SQRT,
              "stddev_pop": _F_VAR_POP | _F_SQRT, "variance": _F_VAR_SAMP, "var_samp": _F_VAR_SAMP,
              "var_pop": _F_VAR_POP}
 _BOOL = {"bool_and": "min", "every": "min", "bool_or": "max", "any": "max", "some": "max"}
-_SUPPORTED = {"count", "sum", "min", "max", "avg", "mean", "count_if", *_VARIANCE, *_BOOL}
+# the other central-moment aggregates → the finishing kind of their M3 / M4 / Cxy word; the last three take a pair
+_MOMENTS = {"skewness": _F_SKEW, "kurtosis": _F_KURT, "covar_pop": _F_COVAR_POP, "covar_samp": _F_COVAR_SAMP,
+            "corr": _F_CORR}
+_PAIRED = ("covar_pop", "covar_samp", "corr")
+_NUMERIC = ("byte", "short", "int", "long", "double", "float")
+_SUPPORTED = {"count", "sum", "min", "max", "avg", "mean", "count_if", *_VARIANCE, *_BOOL, *_MOMENTS}
+
+
+def pair_keys(x, y):
+    """The argument keys of the columns x and y of a pair (x, y) restricted to the rows where both are non-null:
+    their data is the arguments', their validity ``x.valid & y.valid`` (``DenseWindow.accumulate``)."""
+    return ("pair_x", x.key(), y.key()), ("pair_y", x.key(), y.key())
 
 N.register_sigs({
     "dxa_win_live": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
@@ -141,7 +181,8 @@ class _DictCols(ctypes.Structure):
 class _EmitArgs(ctypes.Structure):
     _fields_ = [("acc", ctypes.c_void_p), ("stride", ctypes.c_int32), ("nreq", ctypes.c_int32),
                 ("kind", ctypes.c_int32 * 64), ("pos", ctypes.c_int32 * 64), ("cnt", ctypes.c_int32 * 64),
-                ("dst", ctypes.c_void_p), ("dvalid", ctypes.c_void_p), ("okey", ctypes.c_void_p * MAX_KEY_COLS),
+                ("op2", ctypes.c_int32 * 64), ("op3", ctypes.c_int32 * 64), ("dst", ctypes.c_void_p),
+                ("dvalid", ctypes.c_void_p), ("okey", ctypes.c_void_p * MAX_KEY_COLS),
                 ("olen", ctypes.c_void_p * MAX_KEY_COLS), ("ovalid", ctypes.c_void_p * MAX_KEY_COLS),
                 ("out_idx", ctypes.c_void_p), ("scal", ctypes.c_void_p), ("gcap", ctypes.c_int32)]
 
@@ -166,6 +207,18 @@ class _M2Args(ctypes.Structure):
                 ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class _MomArg(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("cnt", ctypes.c_int32),
+                ("sum", ctypes.c_int32), ("sumy", ctypes.c_int32), ("w0", ctypes.c_int32), ("w1", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+class _MomArgs(ctypes.Structure):
+    _fields_ = [("a", _MomArg * MAX_MOMENTS), ("gid", ctypes.c_void_p), ("row", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("gcap", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -178,7 +231,8 @@ def _sizes() -> List[int]:
         if _SIZES[0] != ctypes.sizeof(_KeyCols) or _SIZES[1] != ctypes.sizeof(_DictCols) or \
                 N.lib().dxa_win_emit_size() != ctypes.sizeof(_EmitArgs) or \
                 N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds) or \
-                N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args):
+                N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args) or \
+                N.lib().dxa_win_mom_size() != ctypes.sizeof(_MomArgs):
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
@@ -192,10 +246,15 @@ def _requests(aggs: Dict):
     "dcount"; every other DISTINCT aggregate is ineligible, and so are more than ``MAX_DISTINCT`` different
     distinct arguments.  The variance family keeps its name (``_VARIANCE``), ``bool_and`` / ``every`` are "min" and
     ``bool_or`` / ``any`` / ``some`` "max" of a boolean result ("bmin" / "bmax"); more than ``MAX_VARIANCE``
-    different variance arguments are ineligible."""
+    different variance arguments are ineligible.  ``skewness`` / ``kurtosis`` (one argument) and ``corr`` /
+    ``covar_pop`` / ``covar_samp`` (two: the arg entry is the tuple (x, y)) keep their names too; each different
+    argument or pair is one job of the pane's moment pass, and more than ``MAX_MOMENTS`` of them are ineligible.  The
+    M2 words they need (skewness / kurtosis: of the argument; corr: of both masked columns of the pair) count as
+    variance arguments."""
     out = []
     dargs = set()
     vargs = set()
+    margs = set()
     for ak, call in aggs.items():
         name = call.name
         if name not in _SUPPORTED:
@@ -210,6 +269,20 @@ def _requests(aggs: Dict):
             continue
         if call.star or (name == "count" and not call.args):
             out.append((ak, "count_star", None))
+            continue
+        if name in _MOMENTS:
+            if len(call.args) != (2 if name in _PAIRED else 1):
+                raise Ineligible(name)
+            if name in _PAIRED:
+                margs.add(pair_keys(*call.args))
+                if name == "corr":
+                    vargs.update(pair_keys(*call.args))
+            else:
+                margs.add(call.args[0].key())
+                vargs.add(call.args[0].key())
+            if len(margs) > MAX_MOMENTS or len(vargs) > MAX_VARIANCE:
+                raise Ineligible("too many moment arguments")
+            out.append((ak, name, tuple(call.args) if name in _PAIRED else call.args[0]))
             continue
         if len(call.args) != 1:
             raise Ineligible(name)
@@ -266,7 +339,10 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     → ``slots`` [(key, agg_multi value kind, combine op)], ``order`` (slot per word, None for padding),
     ``line_ops`` (combine op per 8-word line), ``plan`` [(agg key, kind, slot, count slot, dtype)], ``fin`` /
     ``pfin`` (win_emit_kernel's (kind, word, count word) per aggregate / per partial state), ``m2desc`` and
-    ``m2args`` (the variance arguments' words for win_combine_kernel and win_m2_kernel)."""
+    ``m2args`` (the variance arguments' words for win_combine_kernel and win_m2_kernel).  With skewness / kurtosis
+    / corr / covar_*: their ``fin`` entries are (kind, word, count word, operand 2, operand 3), ``momdesc`` describes
+    the words of the op-4 lines to win_combine_kernel and ``momargs`` [(x key, y key or None, count, sum x, sum y,
+    word 0, word 1)] lists win_mom_kernel's jobs; a pair's slots are keyed by ``pair_keys``."""
     # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
     slots, keyed = [], {}
 
@@ -280,6 +356,9 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     star = slot(("count", None), _MV_COUNT, _MA_ADD_F64)
     plan = []
     m2_of = {}                      # M2 slot → (count slot, sum slot) of the same argument
+    mom_of = {}                     # M3 / M4 / Cxy slot → (kind, the slots its combine reads)
+    mom_jobs = {}                   # argument key or pair keys → [x, y, count, sum x, sum y, word-0, word-1 slot]
+    mom_ops = {}                    # agg key → (operand 2 slot, operand 3 slot) of its finishing kind
     value_only = set()              # aggregates whose partial is the value alone (distagg._partials: bool_and / bool_or)
     for ak, func, arg in reqs:
         if func == "count_star":
@@ -290,8 +369,46 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
             plan.append((ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None))
             continue
+        if func in _PAIRED:
+            # (n, Σx, Σy, Cxy) over the rows where both arguments are non-null: count and sums of the pair's masked
+            # columns, one Cxy word in an op-4 line; corr adds the masked columns' M2 words (the variance machinery)
+            if any(arg_types[a.key()][0] not in _NUMERIC for a in arg):
+                raise Ineligible(f"{func} type")
+            kx, ky = pair_keys(*arg)
+            cnt = slot(("count", kx), _MV_COUNT, _MA_ADD_F64)
+            sx = slot(("sumf", kx), _MV_F64, _MA_ADD_F64)
+            sy = slot(("sumf", ky), _MV_F64, _MA_ADD_F64)
+            cxy = slot(("cxy", (kx, ky)), -1, _MA_MOM)
+            mom_of[cxy] = (_MOM_CXY, cnt, sx, sy)
+            mom_jobs[(kx, ky)] = [kx, ky, cnt, sx, sy, cxy, None]
+            mom_ops[ak] = (None, None)
+            if func == "corr":
+                m2x, m2y = slot(("m2", kx), -1, _MA_M2), slot(("m2", ky), -1, _MA_M2)
+                m2_of[m2x], m2_of[m2y] = (cnt, sx), (cnt, sy)
+                mom_ops[ak] = (m2x, m2y)
+            plan.append((ak, func, cxy, cnt, "double"))
+            continue
         ck = arg.key()
         dtype, is_f = arg_types[ck]
+        if func in _MOMENTS:
+            # (n, Σx, M2, M3[, M4]) of the argument: the words AVG / STDDEV of it use and an M3 word (kurtosis: and
+            # an M4 word, whose combine reads M3) in an op-4 line
+            if dtype not in _NUMERIC:
+                raise Ineligible(f"{func} type")
+            cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
+            sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
+            m2 = slot(("m2", ck), -1, _MA_M2)
+            m2_of[m2] = (cnt, sm)
+            m3 = slot(("m3", ck), -1, _MA_MOM)
+            mom_of[m3] = (_MOM_M3, cnt, sm, m2)
+            job = mom_jobs.setdefault(ck, [ck, None, cnt, sm, None, m3, None])
+            word = m3
+            if func == "kurtosis":
+                word = job[6] = slot(("m4", ck), -1, _MA_MOM)
+                mom_of[word] = (_MOM_M4, cnt, sm, m2, m3)
+            mom_ops[ak] = (m2, None)
+            plan.append((ak, func, word, cnt, "double"))
+            continue
         if func == "count_if":
             # the predicate mask (NULL counts as false) summed as int64; never NULL, so no count word
             plan.append((ak, "cif", slot(("cif", ck), _MV_I64, _MA_ADD_U64), None, "long"))
@@ -325,7 +442,7 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             kind = (_MV_F64_ORD if is_f else _MV_I64) | (_MV_NOT if func == "min" else 0)
             plan.append((ak, "f64" if is_f else "i64", slot((func, ck), kind, _MA_MAX), cnt, dtype))
     order, line_ops = [], []
-    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2):
+    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM):
         mine = [i for i, sl in enumerate(slots) if sl[2] == op]
         for k in range(0, len(mine), 8):
             chunk = mine[k:k + 8]
@@ -345,6 +462,8 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             fin.append((_F_I64, where[s], -1))
         elif kind in _VARIANCE:
             fin.append((_VARIANCE[kind], where[s], where[c]))
+        elif kind in _MOMENTS:
+            fin.append((_MOMENTS[kind], where[s], where[c], *(-1 if o is None else where[o] for o in mom_ops[ak])))
         elif kind == "avg":
             fin.append((_F_AVG, where[s], where[c]))
         elif kind == "sum":
@@ -353,7 +472,8 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             k = (_F_F64_ORD if kind == "f64" else _F_I64) | (_F_NOT if slots[s][1] & _MV_NOT else 0)
             fin.append((k, where[s], where[c]))
     # partial states per aggregate (distagg._partials' suffixes): "cnt" a count, "v" the SUM / MIN / MAX value,
-    # "s" AVG's and the variance family's raw double sum, "m2" the centred sum of squares
+    # "s" AVG's and the variance family's raw double sum, "m2" the centred sum of squares; skewness / kurtosis add
+    # "m3" / "m4", a pair has "sx", "sy", "cxy" (and corr "m2x", "m2y") over its both-non-null rows
     pfin = {}
     for j, (ak, kind, s, c, dt) in enumerate(plan):
         if kind == "count":
@@ -365,6 +485,20 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         elif kind in _VARIANCE:
             pfin[ak] = {"s": (_F_F64, where[m2_of[s][1]], where[c]), "m2": (_F_F64, where[s], where[c]),
                         "cnt": (_F_COUNT, where[c], -1)}
+        elif kind in _PAIRED:
+            _k, _c, sx, sy = mom_of[s]
+            pfin[ak] = {"sx": (_F_F64, where[sx], where[c]), "sy": (_F_F64, where[sy], where[c]),
+                        "cxy": (_F_F64, where[s], where[c]), "cnt": (_F_COUNT, where[c], -1)}
+            if kind == "corr":
+                pfin[ak].update(m2x=(_F_F64, where[mom_ops[ak][0]], where[c]),
+                                m2y=(_F_F64, where[mom_ops[ak][1]], where[c]))
+        elif kind in _MOMENTS:
+            m2 = mom_ops[ak][0]
+            m3 = s if kind == "skewness" else mom_of[s][4]
+            pfin[ak] = {"s": (_F_F64, where[m2_of[m2][1]], where[c]), "m2": (_F_F64, where[m2], where[c]),
+                        "m3": (_F_F64, where[m3], where[c]), "cnt": (_F_COUNT, where[c], -1)}
+            if kind == "kurtosis":
+                pfin[ak]["m4"] = (_F_F64, where[s], where[c])
         elif ak in value_only:
             pfin[ak] = {"v": fin[j]}
         else:
@@ -378,8 +512,18 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         m2desc[where[m2]] = where[c] | where[sm] << 16
         m2args.append((slots[m2][0][1], where[c], where[sm], where[m2]))
     dcount_word = {key[1]: where[i] for i, (key, _k, _o) in enumerate(slots) if key[0] == "dcount"}
-    return dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
-                count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word)
+    out = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
+               count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word)
+    if mom_of:
+        # per op-4 word: kind << 24 | the words it reads, 6 bits each (win_combine_kernel); per argument or pair the
+        # words of its job in the pane's moment pass (win_mom_kernel)
+        momdesc = [0] * stride
+        for sl, (kind, *reads) in mom_of.items():
+            momdesc[where[sl]] = kind << 24 | sum(where[r] << 6 * q for q, r in enumerate(reads))
+        out["momdesc"] = momdesc
+        out["momargs"] = [(kx, ky, where[c], where[sx], -1 if sy is None else where[sy], where[w0],
+                           -1 if w1 is None else where[w1]) for kx, ky, c, sx, sy, w0, w1 in mom_jobs.values()]
+    return out
 
 
 class PairState:
@@ -513,6 +657,7 @@ class DenseWindow:
         self.blocks: Dict[int, tuple] = {}             # block id → (member entry ids, block slot, entries)
         self.layout = None              # built from the first pane's evaluated argument types
         self.m2desc_t = self.m2desc_dev = None  # with variance arguments: win_combine_kernel's M2 descriptor
+        self.momdesc_t = self.momdesc_dev = None        # with op-4 lines: its M3 / M4 / Cxy descriptor
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
         self.free = list(range(ring_slots))    # free pane slots (a heap: the lowest is taken first)
         self.disabled = False
@@ -595,13 +740,18 @@ class DenseWindow:
         self.layout = L
         # agg_multi (host ``line_ops_t``) sees an M2 line as an f64 add line of unused slots, so every pane starts
         # its M2 words at 0.0; the ring kernels (``line_ops_dev``) see MA_M2
-        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op == _MA_M2 else op for op in L["line_ops"]],
+        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op in (_MA_M2, _MA_MOM) else op for op in L["line_ops"]],
                                        dtype=torch.int32)
         self.line_ops_dev = torch.tensor(L["line_ops"], dtype=torch.int32).to(self.device)
         self.m2desc_t = self.m2desc_dev = None
-        if L["m2args"]:
+        self.momdesc_t = self.momdesc_dev = None
+        if L["m2args"] or "momdesc" in L:
             self.m2desc_t = torch.tensor(L["m2desc"], dtype=torch.int32)
             self.m2desc_dev = self.m2desc_t.to(self.device)
+        if "momdesc" in L:
+            # the op-4 combine is the M2 combine's sibling and takes both descriptors (all zero without M2 words)
+            self.momdesc_t = torch.tensor(L["momdesc"], dtype=torch.int32)
+            self.momdesc_dev = self.momdesc_t.to(self.device)
         try:
             self.ring, self.acc, self.keep, self.out_idx = self._alloc_ring(self.gcap)
             for ps in self.pairs:
@@ -730,14 +880,22 @@ class DenseWindow:
                 if arg.key() not in dargs:
                     dargs[arg.key()] = _distinct_arg(evaluate(arg, scope, ctx))
                 continue
-            if arg is None or arg.key() in args:
-                continue
-            c = evaluate(arg, scope, ctx)
-            if isinstance(c, ConstColumn):
-                c = c.materialize()
-            if not isinstance(c, PrimColumn) or is_decimal(c.dtype) or c.data.dim() != 1:
-                raise Ineligible("argument type")
-            args[arg.key()] = c
+            for a in arg if isinstance(arg, tuple) else () if arg is None else (arg,):
+                if a.key() in args:
+                    continue
+                c = evaluate(a, scope, ctx)
+                if isinstance(c, ConstColumn):
+                    c = c.materialize()
+                if not isinstance(c, PrimColumn) or is_decimal(c.dtype) or c.data.dim() != 1:
+                    raise Ineligible("argument type")
+                args[a.key()] = c
+            if isinstance(arg, tuple) and pair_keys(*arg)[0] not in args:
+                # a pair's columns: the arguments' data under the validity "both non-null", built once per pane
+                x, y = args[arg[0].key()], args[arg[1].key()]
+                both = x.valid if y.valid is None else y.valid if x.valid is None else \
+                    x.valid.to(torch.bool) & y.valid.to(torch.bool)
+                kx, ky = pair_keys(*arg)
+                args[kx], args[ky] = PrimColumn(x.dtype, x.data, both), PrimColumn(y.dtype, y.data, both)
         if self.layout is None:
             self._build_layout(keys, args, dargs)
         else:
@@ -767,7 +925,7 @@ class DenseWindow:
                 spec += [0, 0, -1]
                 continue
             key, kind, _op = L["slots"][i]
-            if key[0] in ("dcount", "m2"):         # filled after agg_multi: by the distinct fold / win_m2_kernel
+            if kind == -1 or key[0] == "dcount":   # filled after agg_multi: the distinct fold / win_m2 / win_mom
                 spec += [0, 0, -1]
                 continue
             if key[1] is None:
@@ -810,6 +968,16 @@ class DenseWindow:
             m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
             m.gcap, m.stride, m.nargs = self.gcap, self.stride, len(L["m2args"])
             N.call("dxa_win_m2", ctypes.addressof(m), st)
+        if L.get("momargs") and n > 0:
+            # and the M3 / M4 / Cxy words from the same counts and sums (win_mom_kernel): one sweep per argument or pair
+            m = _MomArgs()
+            for k, (kx, ky, cw, sw, syw, w0, w1) in enumerate(L["momargs"]):
+                d, v = xs[kx]
+                m.a[k] = _MomArg(d.data_ptr(), 0 if ky is None else xs[ky][0].data_ptr(),
+                                 0 if v is None else v.data_ptr(), cw, sw, syw, w0, w1, 0)
+            m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
+            m.gcap, m.stride, m.nargs = self.gcap, self.stride, len(L["momargs"])
+            N.call("dxa_win_mom", ctypes.addressof(m), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
@@ -837,7 +1005,11 @@ class DenseWindow:
         member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
         slots_dev = self._dev_slots(member_slots)
         st = N.stream_handle(self.device)
-        if self.m2desc_dev is not None:
+        if self.momdesc_dev is not None:
+            N.call("dxa_win_combine_block_mom", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
+                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.ptr(self.m2desc_dev),
+                   self.m2desc_t.data_ptr(), N.ptr(self.momdesc_dev), self.momdesc_t.data_ptr(), st)
+        elif self.m2desc_dev is not None:
             N.call("dxa_win_combine_block_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
                    len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.ptr(self.m2desc_dev),
                    self.m2desc_t.data_ptr(), st)
@@ -871,7 +1043,14 @@ class DenseWindow:
                 folds.p[k] = _PairFold(ps.pres.data_ptr(), ps.pitch, ps.keys[0][2].data_ptr(), ps.scal_ptr, ps.pcap,
                                        ps.word)
             folds.n = len(self.pairs)
-        if self.m2desc_dev is not None:
+        if self.momdesc_dev is not None:
+            # a layout with op-4 lines: the combine that also knows the M3 / M4 / Cxy shifts
+            N.call("dxa_win_answer_mom", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
+                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
+                   0 if folds is None else ctypes.addressof(folds), N.ptr(self.m2desc_dev),
+                   self.m2desc_t.data_ptr(), N.ptr(self.momdesc_dev), self.momdesc_t.data_ptr(), st)
+        elif self.m2desc_dev is not None:
             # a layout with M2 lines: the combine that knows Chan's update, with or without distinct folds
             N.call("dxa_win_answer_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
                    N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
@@ -951,7 +1130,7 @@ class DenseWindow:
         for (ak, kind, s, c, dt), (v, ok) in zip(L["plan"], cols):
             if kind in ("count", "cif"):
                 finals[ak] = PrimColumn("long", v)
-            elif kind == "avg" or kind in _VARIANCE:
+            elif kind == "avg" or kind in _VARIANCE or kind in _MOMENTS:
                 finals[ak] = PrimColumn("double", v.view(torch.float64), ok)
             elif kind == "sum":
                 finals[ak] = PrimColumn(dt, v.view(torch.float64) if dt == "double" else v, ok)
@@ -973,8 +1152,9 @@ class DenseWindow:
         ovalid, dvalid = flags[:nk], flags[nk:]
         e = _EmitArgs()
         e.acc, e.stride, e.nreq = self.acc.data_ptr(), self.stride, nr
-        for r, (k, pos, cnt) in enumerate(fin):
+        for r, (k, pos, cnt, *ops) in enumerate(fin):
             e.kind[r], e.pos[r], e.cnt[r] = k, pos, cnt
+            e.op2[r], e.op3[r] = ops or (-1, -1)
         e.dst, e.dvalid = dst.data_ptr(), dvalid.data_ptr()
         for j in range(nk):
             e.okey[j], e.olen[j], e.ovalid[j] = okey[j].data_ptr(), olen[j].data_ptr(), ovalid[j].data_ptr()

@@ -25,6 +25,9 @@
 // COUNT(DISTINCT x) rides on the same ring: a pair dictionary keyed by (group id, x) and one presence byte per ring
 // slot and pair (win_pair_mark), ORed over the window and added into the combined rows between steps 3 and 4
 // (win_distinct_fold) — see the section before the entry points.
+// The variance family (M2) and skewness / kurtosis / corr / covar (M3, M4, Cxy) keep centred sums per pane and group:
+// second passes over the pane fill them (win_m2_kernel, win_mom_kernel) and win_combine merges slots by the multi-way
+// form of Chan's update.
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -39,6 +42,12 @@ enum : int32_t { MA_ADD_U64 = 0, MA_ADD_F64 = 1, MA_MAX_I64 = 2 };
 // the slot's own rows.  agg_multi sees such a line as MA_ADD_F64 with unused slots (every pane starts it at 0.0),
 // win_m2_kernel fills it, and slots are combined with Chan et al.'s update (win_combine_kernel).
 enum : int32_t { MA_M2 = 3 };
+// The other centred words of this file: a group's third and fourth central sums M3 = Σ (x − mean)³, M4 = Σ (x − mean)⁴
+// and the co-moment Cxy = Σ (x − mean_x)(y − mean_y) of a pair, each about the means of the slot's own rows.  All
+// three sit in lines of one combine op; ``momdesc`` says per word which it is and which words of the row it reads
+// (kind << 24 | four 6-bit word indices).  agg_multi sees such a line as unused f64 words, win_mom_kernel fills it.
+enum : int32_t { MA_MOM = 4 };
+enum : int32_t { MOM_M3 = 1, MOM_M4 = 2, MOM_CXY = 3 };
 
 // same layout as hash_groupby.hip's KeyCols (built by dxa/ops/hashing.py key_cols)
 struct KeyCol {
@@ -91,14 +100,23 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
 // (the multi-way form of Chan's update: exact algebra, every term centred), so a block slot holds a valid
 // (n, sum, M2) triple about the block's mean and blocks and loose panes combine by the same formula.  Without kM2
 // the branch is compiled out (dxa_win_live runs that form over any layout: it reads the count word only).
-template <bool kBlock, bool kM2>
+// ``kMom``: the layout has MA_MOM lines and ``momdesc`` [stride] describes each of their words: kind << 24 and the
+// row's words a | b << 6 | c << 12 | d << 18 — a the count, b the sum (of x), then for M3 c = M2; for M4 c = M2,
+// d = M3; for Cxy c = the sum of y.  With δ_s = sum_s / n_s − mean (ε_s the same for y) over the slots with n_s > 0:
+//   M3  = Σ_s [ M3_s + 3 δ_s M2_s + n_s δ_s³ ]
+//   M4  = Σ_s [ M4_s + 4 δ_s M3_s + 6 δ_s² M2_s + n_s δ_s⁴ ]
+//   Cxy = Σ_s [ Cxy_s + n_s δ_s ε_s ]
+// Every right-hand side reads the slots' words only, never a combined word, so each output word is computed on its
+// own like M2.  A padding word of such a line (kind 0) is written as 0.0.  Without kMom the branch is compiled out.
+template <bool kBlock, bool kM2, bool kMom>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
                                                           int32_t nslots_in, int32_t stride,
                                                           const int32_t* __restrict__ line_op,
                                                           const int32_t* __restrict__ scal, int32_t gcap,
                                                           int32_t fixed_rows, unsigned long long* __restrict__ out,
-                                                          const int32_t* __restrict__ m2desc) {
+                                                          const int32_t* __restrict__ m2desc,
+                                                          const int32_t* __restrict__ momdesc) {
   int32_t ng = scal[0];
   if (ng > gcap) ng = gcap;
   const int64_t held = (int64_t)ng * stride;
@@ -133,6 +151,40 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
         if (ns == 0.0) continue;
         const double d = __longlong_as_double((long long)ring[base + si]) / ns - mean;
         acc += __longlong_as_double((long long)ring[base + idx]) + ns * d * d;
+      }
+      out[idx] = (unsigned long long)__double_as_longlong(acc);
+    } else if (kMom && op == MA_MOM) {
+      const int32_t dsc = momdesc[w];
+      const int kind = dsc >> 24;
+      const int64_t r0 = idx - w;
+      const int64_t ci = r0 + (dsc & 63), si = r0 + ((dsc >> 6) & 63), ti = r0 + ((dsc >> 12) & 63),
+                    ui = r0 + ((dsc >> 18) & 63);
+      const int ns_in = kind ? nslots : 0;
+      double n = 0.0, sum = 0.0, sumy = 0.0;
+      for (int s = 0; s < ns_in; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        n += __longlong_as_double((long long)ring[base + ci]);
+        sum += __longlong_as_double((long long)ring[base + si]);
+        if (kind == MOM_CXY) sumy += __longlong_as_double((long long)ring[base + ti]);
+      }
+      const double den = n > 0.0 ? n : 1.0;
+      const double mean = sum / den, meany = sumy / den;
+      double acc = 0.0;
+      for (int s = 0; s < ns_in; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        const double ns = __longlong_as_double((long long)ring[base + ci]);
+        if (ns == 0.0) continue;
+        const double d = __longlong_as_double((long long)ring[base + si]) / ns - mean;
+        const double own = __longlong_as_double((long long)ring[base + idx]);
+        const double t = __longlong_as_double((long long)ring[base + ti]);     // M2_s, or the slot's sum of y
+        if (kind == MOM_CXY) {
+          acc += own + ns * d * (t / ns - meany);
+        } else if (kind == MOM_M3) {
+          acc += own + 3.0 * d * t + ns * d * d * d;
+        } else {
+          const double m3 = __longlong_as_double((long long)ring[base + ui]);
+          acc += own + 4.0 * d * m3 + 6.0 * d * d * t + ns * d * d * d * d;
+        }
       }
       out[idx] = (unsigned long long)__double_as_longlong(acc);
     } else {
@@ -247,7 +299,79 @@ __global__ __launch_bounds__(256) void win_m2_kernel(const M2Args m) {
   }
 }
 
+// 2c. the same second pass for the MA_MOM words (skewness / kurtosis: M3 and M4 of an argument; corr / covar: Cxy
+// of a pair of arguments whose validity is already "both non-null"): d = x − sum_g / n_g as above, and d³, d⁴ or
+// d_x · d_y go into the group's words.  One sweep per argument (or pair) adds all of its words — the row's group id,
+// value and the dependent read of the group's sum and count are fetched once for M3 and M4 — through two LDS arrays
+// (16 KB: the occupancy stays bounded by the 512-workgroup grid, not by LDS).  Ids below kM2LdsGroups are summed in
+// LDS and flushed with one global add per touched group, word and workgroup; the others add straight to the row.
+constexpr int kMaxMomArgs = 8;
+struct MomArg {
+  const double* x;
+  const double* y;         // null: M3 (w0) and, with w1 >= 0, M4 (w1) of x; else Cxy (w0) of (x, y)
+  const uint8_t* valid;
+  int32_t cnt;             // words of the slot row: the count, the sum of x, the sum of y, the output words
+  int32_t sum;
+  int32_t sumy;
+  int32_t w0;
+  int32_t w1;
+  int32_t pad;
+};
+struct MomArgs {
+  MomArg a[kMaxMomArgs];
+  const int32_t* gid;
+  double* row;             // the ring slot: [gcap + 1][stride]
+  int64_t n;
+  int32_t gcap;
+  int32_t stride;
+  int32_t nargs;
+  int32_t pad;
+};
 
+__global__ __launch_bounds__(256) void win_mom_kernel(const MomArgs m) {
+  __shared__ double part[2][kM2LdsGroups];
+  const int32_t lds_groups = m.gcap < kM2LdsGroups ? m.gcap : kM2LdsGroups;
+  for (int k = 0; k < m.nargs; ++k) {
+    const MomArg a = m.a[k];
+    const bool two = a.w1 >= 0;
+    for (int g = threadIdx.x; g < kM2LdsGroups; g += blockDim.x) {
+      part[0][g] = 0.0;
+      part[1][g] = 0.0;
+    }
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m.n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int32_t g = m.gid[i];
+      if (g < 0 || g >= m.gcap || (a.valid && !a.valid[i])) continue;
+      double* r = m.row + (int64_t)g * m.stride;
+      const double nn = r[a.cnt];                          // the row itself was counted: n_g ≥ 1
+      const double d = a.x[i] - r[a.sum] / nn;
+      double v0, v1 = 0.0;
+      if (a.y) {
+        v0 = d * (a.y[i] - r[a.sumy] / nn);
+      } else {
+        v0 = d * d * d;
+        v1 = v0 * d;
+      }
+      if (g < kM2LdsGroups) {
+        atomicAdd(&part[0][g], v0);
+        if (two) atomicAdd(&part[1][g], v1);
+      } else {
+        atomicAdd(r + a.w0, v0);
+        if (two) atomicAdd(r + a.w1, v1);
+      }
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < lds_groups; g += blockDim.x) {
+      const double v = part[0][g];
+      if (v != 0.0) atomicAdd(m.row + (int64_t)g * m.stride + a.w0, v);
+      if (two) {
+        const double u = part[1][g];
+        if (u != 0.0) atomicAdd(m.row + (int64_t)g * m.stride + a.w1, u);
+      }
+    }
+    __syncthreads();
+  }
+}
 
 __device__ __forceinline__ uint64_t row_hash(const KeyCols& a, int64_t i) {
   uint64_t h = 0;
@@ -377,6 +501,12 @@ __global__ void win_insert_kernel(const KeyCols a, DictCols d, const uint8_t* __
 constexpr int kMaxEmit = 64;
 enum : int { F_COUNT = 0, F_I64 = 1, F_F64 = 2, F_AVG = 3, F_F64_ORD = 4, F_VAR_SAMP = 5, F_VAR_POP = 6, F_NOT = 8,
              F_SQRT = 16 };
+// The kinds with more operands live in bits 5-7 (their low three bits are 0): pos = Cxy / M3 / M4, cnt = n and
+//   F_COVAR_POP  Cxy / n                       F_COVAR_SAMP  Cxy / (n − 1), NaN for n = 1
+//   F_CORR       Cxy / sqrt(M2x · M2y), op2 = M2x, op3 = M2y; NaN unless M2x · M2y > 0
+//   F_SKEW       sqrt(n) · M3 / M2^1.5, op2 = M2;  F_KURT  n · M4 / M2² − 3, op2 = M2; NaN unless M2 > 0
+// (Spark 2.4's Covariance / Corr / CentralMomentAgg; n = 0 is NULL by the validity rule, as everywhere).
+enum : int { F_COVAR_POP = 32, F_COVAR_SAMP = 64, F_CORR = 96, F_SKEW = 128, F_KURT = 160, F_KIND_MASK = 7 | 224 };
 struct EmitArgs {
   const long long* acc;
   int32_t stride;
@@ -384,6 +514,8 @@ struct EmitArgs {
   int32_t kind[kMaxEmit];
   int32_t pos[kMaxEmit];
   int32_t cnt[kMaxEmit];
+  int32_t op2[kMaxEmit];         // further words of the kinds above F_SQRT (unused: -1)
+  int32_t op3[kMaxEmit];
   long long* dst;                // [nreq][gcap]
   uint8_t* dvalid;               // [nreq][gcap]
   int64_t* okey[kMaxKeyCols];    // [gcap] int64 key words, or the strings' starts in the dictionary arena
@@ -415,7 +547,7 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
       if (k & F_NOT) v = ~v;
       const double c = e.cnt[r] >= 0 ? __longlong_as_double(row[e.cnt[r]]) : 1.0;
       long long o;
-      switch (k & 7) {
+      switch (k & F_KIND_MASK) {
         case F_COUNT: o = (long long)__longlong_as_double(v); break;
         case F_AVG: o = __double_as_longlong(__longlong_as_double(v) / (c > 1.0 ? c : 1.0)); break;
         case F_F64_ORD: o = v < 0 ? (v ^ 0x7fffffffffffffffll) : v; break;
@@ -423,12 +555,35 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
         case F_VAR_POP: {
           // pos = the M2 word, cnt = the count word n: M2 / (n − 1) or M2 / n; Spark 2.4's sample statistic of
           // one row is NaN (n = 0 is NULL by the validity rule below)
-          const bool samp = (k & 7) == F_VAR_SAMP;
+          const bool samp = (k & F_KIND_MASK) == F_VAR_SAMP;
           const double den = samp ? c - 1.0 : c;
           double r = __longlong_as_double(v) / (den > 0.0 ? den : 1.0);
           if (samp && c == 1.0) r = __longlong_as_double(0x7ff8000000000000ll);
           if (k & F_SQRT) r = sqrt(r);
           o = __double_as_longlong(r);
+          break;
+        }
+        case F_COVAR_POP: o = __double_as_longlong(__longlong_as_double(v) / (c > 1.0 ? c : 1.0)); break;
+        case F_COVAR_SAMP: {
+          double r = __longlong_as_double(v) / (c > 1.0 ? c - 1.0 : 1.0);
+          if (!(c > 1.0)) r = __longlong_as_double(0x7ff8000000000000ll);
+          o = __double_as_longlong(r);
+          break;
+        }
+        case F_CORR: {
+          const double p = __longlong_as_double(row[e.op2[r]]) * __longlong_as_double(row[e.op3[r]]);
+          o = p > 0.0 ? __double_as_longlong(__longlong_as_double(v) / sqrt(p)) : 0x7ff8000000000000ll;
+          break;
+        }
+        case F_SKEW: {
+          const double m2 = __longlong_as_double(row[e.op2[r]]);
+          o = m2 > 0.0 ? __double_as_longlong(sqrt(c) * __longlong_as_double(v) / (m2 * sqrt(m2)))
+                       : 0x7ff8000000000000ll;
+          break;
+        }
+        case F_KURT: {
+          const double m2 = __longlong_as_double(row[e.op2[r]]);
+          o = m2 > 0.0 ? __double_as_longlong(c * __longlong_as_double(v) / (m2 * m2) - 3.0) : 0x7ff8000000000000ll;
           break;
         }
         default: o = v; break;
@@ -656,9 +811,9 @@ DXA_API int dxa_win_combine(const void* ring, int32_t gcap, int32_t stride, cons
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+  hipLaunchKernelGGL((win_combine_kernel<false, false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
                      s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc, (const int32_t*)nullptr);
+                     (unsigned long long*)acc, (const int32_t*)nullptr, (const int32_t*)nullptr);
   hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
                      (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
   hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
@@ -672,9 +827,9 @@ DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, cons
   hipStream_t s = (hipStream_t)st;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL((win_combine_kernel<true, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
+  hipLaunchKernelGGL((win_combine_kernel<true, false, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
                      dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, gcap + 1, r + (int64_t)dst * slot_words, (const int32_t*)nullptr);
+                     gcap, gcap + 1, r + (int64_t)dst * slot_words, (const int32_t*)nullptr, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -813,9 +968,9 @@ DXA_API int dxa_win_answer_distinct(const void* ring, int32_t gcap, int32_t stri
       return (int)hipErrorInvalidValue;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
+  hipLaunchKernelGGL((win_combine_kernel<false, false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
                      s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc, (const int32_t*)nullptr);
+                     (unsigned long long*)acc, (const int32_t*)nullptr, (const int32_t*)nullptr);
   for (int k = 0; k < pf.n; ++k)
     hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
                        dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
@@ -866,9 +1021,9 @@ DXA_API int dxa_win_combine_block_m2(void* ring, int32_t gcap, int32_t stride, c
   if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride)) return (int)hipErrorInvalidValue;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL((win_combine_kernel<true, true>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
+  hipLaunchKernelGGL((win_combine_kernel<true, true, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
                      dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, gcap + 1, r + (int64_t)dst * slot_words, m2desc);
+                     gcap, gcap + 1, r + (int64_t)dst * slot_words, m2desc, (const int32_t*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -887,9 +1042,9 @@ DXA_API int dxa_win_answer_m2(const void* ring, int32_t gcap, int32_t stride, co
       return (int)hipErrorInvalidValue;
   const int64_t slot_words = (int64_t)(gcap + 1) * stride;
   hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, true>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
+  hipLaunchKernelGGL((win_combine_kernel<false, true, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
                      dim3(256), 0, s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, 0, (unsigned long long*)acc, m2desc);
+                     gcap, 0, (unsigned long long*)acc, m2desc, (const int32_t*)nullptr);
   for (int k = 0; k < pf.n; ++k)
     hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
                        dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
@@ -897,6 +1052,92 @@ DXA_API int dxa_win_answer_m2(const void* ring, int32_t gcap, int32_t stride, co
                      (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
   hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
   hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *(const EmitArgs*)emit,
+                     *(const DictCols*)dictcols);
+  return (int)hipGetLastError();
+}
+
+// ---- CORR / COVAR / SKEWNESS / KURTOSIS: entry points -------------------------------------------------------------
+
+DXA_API int dxa_win_mom_size() { return (int)sizeof(MomArgs); }
+
+// a pane's M3 / M4 / Cxy words, on the same stream after dxa_aggregate_multi filled the slot (win_mom_kernel)
+DXA_API int dxa_win_mom(const void* args, void* st) {
+  const MomArgs& m = *(const MomArgs*)args;
+  if (m.nargs < 0 || m.nargs > kMaxMomArgs || m.gcap < 0 || m.stride <= 0) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < m.nargs; ++k) {
+    const MomArg& a = m.a[k];
+    if (a.cnt < 0 || a.cnt >= m.stride || a.sum < 0 || a.sum >= m.stride || a.w0 < 0 || a.w0 >= m.stride ||
+        a.w1 >= m.stride || !a.x || (a.y && (a.sumy < 0 || a.sumy >= m.stride || a.w1 >= 0)))
+      return (int)hipErrorInvalidValue;
+  }
+  if (m.n <= 0 || m.nargs == 0) return 0;
+  hipLaunchKernelGGL(win_mom_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
+  return (int)hipGetLastError();
+}
+
+static bool momdesc_ok(const int32_t* host_desc, int32_t stride) {
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d < 0 || (d >> 24) > MOM_CXY) return false;
+    if (!d) continue;
+    for (int q = 0; q < 24; q += 6)
+      if (((d >> q) & 63) >= stride) return false;
+  }
+  return true;
+}
+
+// dxa_win_combine_block_m2 for a layout that also has MA_MOM lines (``m2desc`` is all zero without M2 lines)
+DXA_API int dxa_win_combine_block_mom(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                                      const int32_t* line_op, int32_t dst, const int32_t* scal,
+                                      const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
+                                      const int32_t* momdesc_host, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride) || !momdesc || !momdesc_host ||
+      !momdesc_ok(momdesc_host, stride) || stride > 64)
+    return (int)hipErrorInvalidValue;
+  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+  unsigned long long* r = (unsigned long long*)ring;
+  hipLaunchKernelGGL((win_combine_kernel<true, true, true>),
+                     dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)), dim3(256), 0, s,
+                     (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal, gcap, gcap + 1,
+                     r + (int64_t)dst * slot_words, m2desc, momdesc);
+  return (int)hipGetLastError();
+}
+
+// dxa_win_answer_m2 for a layout that also has MA_MOM lines (``folds`` may be null: no distinct counts)
+DXA_API int dxa_win_answer_mom(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                               const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
+                               int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
+                               const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
+                               const int32_t* momdesc_host, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride) || !momdesc || !momdesc_host ||
+      !momdesc_ok(momdesc_host, stride) || stride > 64)
+    return (int)hipErrorInvalidValue;
+  const EmitArgs& ea = *(const EmitArgs*)emit;
+  for (int r = 0; r < ea.nreq && r < kMaxEmit; ++r)
+    if ((ea.kind[r] & F_KIND_MASK) >= F_COVAR_POP &&
+        (((ea.kind[r] & F_KIND_MASK) >= F_CORR && (ea.op2[r] < 0 || ea.op2[r] >= stride)) ||
+         ((ea.kind[r] & F_KIND_MASK) == F_CORR && (ea.op3[r] < 0 || ea.op3[r] >= stride))))
+      return (int)hipErrorInvalidValue;
+  PairFolds none{};
+  const PairFolds& pf = folds ? *(const PairFolds*)folds : none;
+  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < pf.n; ++k)
+    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
+      return (int)hipErrorInvalidValue;
+  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+  hipMemsetAsync(scal + 2, 0, 4, s);
+  hipLaunchKernelGGL((win_combine_kernel<false, true, true>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
+                     dim3(256), 0, s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal,
+                     gcap, 0, (unsigned long long*)acc, m2desc, momdesc);
+  for (int k = 0; k < pf.n; ++k)
+    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
+                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
+  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
+  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, ea,
                      *(const DictCols*)dictcols);
   return (int)hipGetLastError();
 }

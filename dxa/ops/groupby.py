@@ -323,6 +323,11 @@ _F_COUNT, _F_I64, _F_F64, _F_AVG, _F_F64_ORD, _F_NOT = 0, 1, 2, 3, 4, 8       # 
 # the finishing kinds M2 / (n - 1), M2 / n with the flag "then the square root"
 _MA_M2 = 3
 _F_VAR_SAMP, _F_VAR_POP, _F_SQRT = 5, 6, 16
+# the same for the M3 / M4 / Cxy words of skewness, kurtosis, corr and covar_*: one combine op, described per word by
+# kind << 24 | four 6-bit word indices, and finishing kinds with further operands in bits 5-7
+_MA_MOM = 4
+_MOM_M3, _MOM_M4, _MOM_CXY = 1, 2, 3
+_F_COVAR_POP, _F_COVAR_SAMP, _F_CORR, _F_SKEW, _F_KURT = 32, 64, 96, 128, 160
 _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096

@@ -1,0 +1,559 @@
+"""CORR, COVAR_POP / COVAR_SAMP, SKEWNESS and KURTOSIS over sliding windows: from the dense ring (window_dense.py
+``plan_layout`` / ``DenseWindow.accumulate``, window_ring.hip win_mom_kernel / win_combine_kernel's op-4 branch /
+win_emit_kernel's new kinds) and from mergeable partial states (distagg.py).  The oracle is the CPU evaluator over the
+materialised window (``query._moments``: two passes over all rows, no GPU code and no merge in it).
+
+Keys, counts and NULL / NaN patterns compare exactly.  Covariances (and the variance family beside them) compare with
+``rel=1e-9, abs=1e-12``; the dimensionless results (corr, skewness, kurtosis) with ``abs=1e-9`` and no relative test —
+a near-zero skewness has no meaningful relative error.  Basis: merging random splits of ≤ 2048 rows per group with
+the multi-way shift formulas deviates from a direct two-pass by at most 2e-15 absolute (dimensionless) and 5e-16
+relative (covariances) for exactly summable values below 64, so the tolerances sit six orders above the arithmetic
+and orders below a dropped term (``temp`` is skewed on purpose: M3 is far from 0).  The offset case (values + 1e9)
+deviated by at most 2e-9 absolute and 3e-10 relative and uses ``rel=1e-6`` / ``abs=1e-6``.  Every stream prints the
+largest deviations it saw (``-s``); the recorded ones are in profiles/window_comoments/README.md."""
+import math
+
+import pytest
+import torch
+
+from dxa.engine.column import PrimColumn, Table, strings_from_pylist
+from dxa.engine.expr import EvalContext
+from dxa.engine.query import Catalog, run_sql
+from dxa.engine.windows import TimeWindowConf, WindowStore
+
+S = 1_000_000
+REL, ABS = 1e-9, 1e-12
+DIMLESS_ABS = 1e-9
+DIMLESS = ("cr", "sk", "ku", "kh")           # result columns of corr / skewness / kurtosis, by name
+Q_ALL = ("SELECT deviceId, COUNT(*) AS c, AVG(temp) AS av, STDDEV(temp) AS sd, VAR_POP(hum) AS vp, "
+         "COUNT(DISTINCT kind) AS dk, corr(temp, hum) AS cr, covar_pop(temp, hum) AS cp, covar_samp(temp, hum) AS cs, "
+         "skewness(temp) AS sk, kurtosis(temp) AS ku, kurtosis(hum * 2 + deviceId) AS kh "
+         "FROM W WHERE kind != 'c' GROUP BY deviceId")
+Q_EDGE = ("SELECT deviceId, COUNT(*) AS c, COUNT(temp) AS n, covar_pop(temp, hum) AS cp, covar_samp(temp, hum) AS cs, "
+          "corr(temp, hum) AS cr, skewness(temp) AS sk, kurtosis(temp) AS ku FROM W GROUP BY deviceId")
+Q_OFFSET = ("SELECT deviceId, corr(temp + 1000000000.0, hum + 1000000000.0) AS cr, "
+            "covar_pop(temp + 1000000000.0, hum + 1000000000.0) AS cp, "
+            "covar_samp(temp + 1000000000.0, hum + 1000000000.0) AS cs, skewness(temp + 1000000000.0) AS sk, "
+            "kurtosis(hum + 1000000000.0) AS ku FROM W GROUP BY deviceId")
+Q_FIVE = ("SELECT deviceId, COUNT(*) AS c, corr(temp, hum) AS cr, covar_pop(temp, hum) AS cp, "
+          "covar_samp(hum, temp) AS cs, skewness(temp) AS sk, kurtosis(temp) AS ku FROM W GROUP BY deviceId")
+Q_MOD = ("SELECT deviceId % 3 AS m, COUNT(*) AS c, corr(temp, hum) AS cr, skewness(temp) AS sk, kurtosis(hum) AS ku "
+         "FROM W GROUP BY deviceId % 3")
+Q_DGLOB = ("SELECT COUNT(DISTINCT deviceId) AS dd, corr(temp, hum) AS cr, covar_samp(temp, hum) AS cs, "
+           "skewness(temp) AS sk, count_if(temp > 32) AS ci FROM W WHERE temp > 8")
+Q_DNONE = ("SELECT COUNT(DISTINCT deviceId) AS dd, corr(temp, hum) AS cr, covar_samp(temp, hum) AS cs, "
+           "skewness(temp) AS sk, count_if(temp > 32) AS ci FROM W WHERE temp > 1000")                  # never a row
+Q_INT = ("SELECT deviceId, COUNT(*) AS c, SUM(temp) AS s, MIN(temp) AS mn, MAX(temp) AS mx, AVG(temp) AS av "
+         "FROM W GROUP BY deviceId")
+Q_SD = ("SELECT deviceId, COUNT(*) AS c, AVG(temp) AS av, STDDEV(temp) AS sd, VAR_POP(temp) AS vp FROM W "
+        "GROUP BY deviceId")
+STABLE = 200
+SEEN = {"rel": 0.0, "abs": 0.0, "dimless": 0.0}
+
+
+# ---- helpers (copies of tests/test_window_dense_moments.py's, with a second numeric column ``hum``) -----------------
+def drifting_ids(rng, b, n):
+    """Batch ``b``'s drifting ids: uniform in [4b, 4b + 12)."""
+    return rng.integers(4 * b, 4 * b + 12, n)
+
+
+def batch(rng, t_us, ids, spread=S - 1, temp=None, temp_valid=None, hum_valid=None):
+    """A batch with given device ids; event times within ``spread`` before the batch time.  ``temp`` is the square of
+    a uniform multiple of 0.25 below 8 (a multiple of 1/16 below 64: exactly summable and visibly skewed), ``hum`` a
+    multiple of 0.25 below 64 that depends on ``temp``; each has NULLs of its own."""
+    import numpy as np
+    n = len(ids)
+    ts = torch.tensor([t_us - int(rng.integers(0, spread)) for _ in range(n)], dtype=torch.int64)
+    tv = (rng.integers(0, 32, n) * 0.25) ** 2
+    if temp is not None:
+        tv = np.asarray(temp, dtype=np.float64)
+    hv = np.floor(tv * 2) * 0.25 + rng.integers(0, 128, n) * 0.25
+    tvalid = rng.random(n) > 0.1
+    hvalid = rng.random(n) > 0.15
+    if temp_valid is not None:
+        tvalid = np.asarray(temp_valid)
+    if hum_valid is not None:
+        hvalid = np.asarray(hum_valid)
+    kinds = strings_from_pylist([["a", "b", "c"][int(i) % 3] for i in rng.integers(0, 3, n)], "cpu")
+    return Table(["ts", "deviceId", "kind", "temp", "hum"],
+                 [PrimColumn("timestamp", ts), PrimColumn("long", torch.tensor(ids, dtype=torch.int64)), kinds,
+                  PrimColumn("double", torch.tensor(tv, dtype=torch.float64), torch.tensor(tvalid)),
+                  PrimColumn("double", torch.tensor(hv, dtype=torch.float64), torch.tensor(hvalid))], n, "cpu")
+
+
+def churn_stream(nb, spread=S - 1):
+    """200 rows per batch over the drifting ids → [(batch time, CPU table, ids)]."""
+    import numpy as np
+    rng = np.random.default_rng(23)
+    out = []
+    for b in range(nb):
+        ids = drifting_ids(rng, b, 200)
+        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
+    return out
+
+
+def stable_stream(nb, drift, spread=S - 1):
+    """300 rows per batch: 200 over the stable ids and 100 over the drifting ids (or all 300 stable)."""
+    import numpy as np
+    rng = np.random.default_rng(29)
+    out = []
+    for b in range(nb):
+        ids = rng.integers(1000, 1000 + STABLE, 300)
+        if drift:
+            ids[200:] = drifting_ids(rng, b, 100)
+        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
+    return out
+
+
+def rows_of(t):
+    """The table's rows as dicts of Python values (NULL as None), in a canonical order."""
+    t = t.to("cpu")
+    cols = {nm: t.column(nm).to_pylist() for nm in t.names}
+    rows = [{nm: cols[nm][i] for nm in t.names} for i in range(t.length)]
+    exact = [nm for nm in t.names if not any(isinstance(r[nm], float) for r in rows)]
+    return sorted(rows, key=lambda r: tuple(repr(r[nm]) for nm in exact))
+
+
+def oracle(q, view):
+    """The CPU evaluator's rows for statement ``q`` over the materialised window ``view``."""
+    mat = Table(view.names, view.columns, view.length, view._device)
+    cat = Catalog()
+    cat.register("W", mat.to("cpu"))
+    return rows_of(run_sql(q, cat, EvalContext(now_us=0)))
+
+
+def assert_rows(got, want, rel, abs_, dimless_abs, what):
+    """Keys, counts, NULLs and NaNs exactly; the columns named in ``DIMLESS`` within ``dimless_abs`` (no relative
+    test), other doubles within ``max(rel · |want|, abs_)``."""
+    assert len(got) == len(want), (what, len(got), len(want))
+    for g, w in zip(got, want):
+        assert g.keys() == w.keys(), what
+        for nm in w:
+            a, b = g[nm], w[nm]
+            if isinstance(a, float) and isinstance(b, float):
+                if math.isnan(a) or math.isnan(b):
+                    assert math.isnan(a) and math.isnan(b), (what, nm, g, w)
+                    continue
+                dev = abs(a - b)
+                if nm in DIMLESS:
+                    SEEN["dimless"] = max(SEEN["dimless"], dev)
+                    assert dev <= dimless_abs, (what, nm, a, b, g, w)
+                    continue
+                if dev > abs_:                      # (below the absolute tolerance a ratio says nothing)
+                    SEEN["rel"] = max(SEEN["rel"], dev / abs(b) if b else math.inf)
+                SEEN["abs"] = max(SEEN["abs"], dev)
+                assert dev <= max(rel * abs(b), abs_), (what, nm, a, b, g, w)
+            else:
+                assert type(a) is type(b) and a == b, (what, nm, g, w)
+
+
+def new_store(win=6):
+    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
+
+
+def dense_states(store):
+    return store.__dict__.get("_dense", {})
+
+
+def set_caps(monkeypatch, groups, groups_max, pairs, pairs_max, block=None):
+    from dxa.engine import window_dense
+    monkeypatch.setattr(window_dense, "DENSE_GROUPS", groups)
+    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", groups_max)
+    monkeypatch.setattr(window_dense, "DENSE_PAIRS", pairs)
+    monkeypatch.setattr(window_dense, "DENSE_PAIRS_MAX", pairs_max)
+    if block is not None:
+        monkeypatch.setattr(window_dense, "BLOCK", block)
+
+
+def run_stream(stream, qs, dev, store, each=None, rel=REL, abs_=ABS, dimless_abs=DIMLESS_ABS, prepare=None):
+    """Every statement over every batch's window equals the CPU oracle; ``each(b, q, rows)`` after each."""
+    SEEN["rel"] = SEEN["abs"] = SEEN["dimless"] = 0.0
+    for b, (T, tbl, _ids) in enumerate(stream):
+        views, _ = store.process(tbl.to(dev), T, S)
+        if prepare is not None:
+            prepare(views["W"])
+        for q in qs:
+            cat = Catalog()
+            cat.register("W", views["W"])
+            rows = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
+            assert_rows(rows, oracle(q, views["W"]), rel, abs_, dimless_abs, (b, q))
+            if each is not None:
+                each(b, q, rows)
+    print(f"largest deviation from the oracle: relative {SEEN['rel']:.3e}, absolute {SEEN['abs']:.3e}, "
+          f"dimensionless (absolute) {SEEN['dimless']:.3e}")
+
+
+def only_state(store):
+    states = list(dense_states(store).values())
+    assert len(states) == 1
+    return states[0]
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------
+def _aggs(*select_items):
+    from dxa.engine.query import _collect_aggs
+    from dxa.sql.parser import parse_select_item
+    aggs = {}
+    for item in select_items:
+        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
+    assert aggs
+    return aggs
+
+
+def _types(reqs, kind=("double", True)):
+    out = {}
+    for _, _f, arg in reqs:
+        for a in arg if isinstance(arg, tuple) else () if arg is None else (arg,):
+            out[a.key()] = kind
+    return out
+
+
+def test_layout_of_the_comoment_aggregates():
+    """``_requests`` accepts the five names; skewness, STDDEV and AVG of one argument share its count, sum and M2
+    words; corr / covar_pop / covar_samp of one (x, y) share the pair's words; the new words sit in the one op-4
+    line, unused by agg_multi and described to the combine by the words they read; ``pfin`` carries the partial
+    states of ``distagg._partials``."""
+    from dxa.engine.window_dense import MAX_VARIANCE, Ineligible, _requests, pair_keys, plan_layout
+    from dxa.ops.groupby import (_F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP, _F_F64, _F_KURT, _F_SKEW, _F_SQRT,
+                                 _F_VAR_SAMP, _MA_ADD_F64, _MA_M2, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4)
+    aggs = _aggs("COUNT(*)", "AVG(temp)", "STDDEV(temp)", "skewness(temp)", "kurtosis(temp)", "corr(temp, hum)",
+                 "covar_pop(temp, hum)", "covar_samp(temp, hum)", "skewness(hum)")
+    reqs = _requests(aggs)
+    assert [f for _, f, _ in reqs] == ["count_star", "avg", "stddev", "skewness", "kurtosis", "corr", "covar_pop",
+                                       "covar_samp", "skewness"]
+    L = plan_layout(reqs, _types(reqs))
+    by_func = {}
+    for j, (_, f, _a) in enumerate(reqs):
+        by_func.setdefault(f, L["fin"][j])
+    pby = {}
+    for ak, f, _a in reqs:
+        pby.setdefault(f, L["pfin"][ak])
+    temp = reqs[1][2].key()
+    px, py = pair_keys(*reqs[5][2])
+    slot_keys = [s[0] for s in L["slots"]]
+    # one count, sum, M2, M3 and M4 slot for temp, shared by AVG, STDDEV, skewness and kurtosis
+    assert [k for k in slot_keys if k[1] == temp] == [("count", temp), ("sumf", temp), ("m2", temp), ("m3", temp),
+                                                      ("m4", temp)]
+    # one pair: count, two sums, Cxy and (for corr) two M2s, shared by the three two-argument aggregates
+    assert [k for k in slot_keys if k[0] == "cxy"] == [("cxy", (px, py))]
+    assert [k for k in slot_keys if k[1] in (px, py)] == [("count", px), ("sumf", px), ("sumf", py), ("m2", px),
+                                                          ("m2", py)]
+    assert L["line_ops"] == [_MA_ADD_F64, _MA_M2, _MA_MOM] and L["stride"] == 24
+    where = {i: w for w, i in enumerate(L["order"]) if i is not None}
+    word = {k: where[i] for i, k in enumerate(slot_keys)}
+    new_words = sorted(w for k, w in word.items() if k[0] in ("m3", "m4", "cxy"))
+    assert new_words == [16, 17, 18, 19]                                # temp's M3, M4, the pair's Cxy, hum's M3
+    assert [w for w, d in enumerate(L["momdesc"]) if d] == new_words
+    # agg_multi never accumulates into a new word
+    assert all(s[1] == -1 for s in L["slots"] if s[0][0] in ("m3", "m4", "cxy"))
+    c, sm, m2 = word[("count", temp)], word[("sumf", temp)], word[("m2", temp)]
+    m3, m4 = word[("m3", temp)], word[("m4", temp)]
+    assert L["momdesc"][m3] == _MOM_M3 << 24 | c | sm << 6 | m2 << 12
+    assert L["momdesc"][m4] == _MOM_M4 << 24 | c | sm << 6 | m2 << 12 | m3 << 18
+    pc, psx, psy, cxy = word[("count", px)], word[("sumf", px)], word[("sumf", py)], word[("cxy", (px, py))]
+    assert L["momdesc"][cxy] == _MOM_CXY << 24 | pc | psx << 6 | psy << 12
+    assert L["m2desc"][m2] == c | sm << 16 and L["m2desc"][word[("m2", py)]] == pc | psy << 16
+    assert (temp, None, c, sm, -1, m3, m4) in L["momargs"] and (px, py, pc, psx, psy, cxy, -1) in L["momargs"]
+    assert len(L["momargs"]) == 3
+    # finishing kinds: existing ones stay 3-tuples, the new ones carry their operands
+    assert by_func["stddev"] == (_F_VAR_SAMP | _F_SQRT, m2, c)
+    assert by_func["skewness"] == (_F_SKEW, m3, c, m2, -1) and by_func["kurtosis"] == (_F_KURT, m4, c, m2, -1)
+    assert by_func["corr"] == (_F_CORR, cxy, pc, word[("m2", px)], word[("m2", py)])
+    assert by_func["covar_pop"] == (_F_COVAR_POP, cxy, pc, -1, -1)
+    assert by_func["covar_samp"] == (_F_COVAR_SAMP, cxy, pc, -1, -1)
+    # partial states, as distagg._partials names them
+    assert pby["skewness"] == {"s": (_F_F64, sm, c), "m2": (_F_F64, m2, c), "m3": (_F_F64, m3, c),
+                               "cnt": (_F_COUNT, c, -1)}
+    assert pby["kurtosis"] == dict(pby["skewness"], m4=(_F_F64, m4, c))
+    assert pby["covar_pop"] == {"sx": (_F_F64, psx, pc), "sy": (_F_F64, psy, pc), "cxy": (_F_F64, cxy, pc),
+                                "cnt": (_F_COUNT, pc, -1)}
+    assert pby["covar_samp"] == pby["covar_pop"]
+    assert pby["corr"] == dict(pby["covar_pop"], m2x=(_F_F64, word[("m2", px)], pc),
+                               m2y=(_F_F64, word[("m2", py)], pc))
+    # a statement without a new aggregate keeps today's layout, word for word
+    old = _requests(_aggs("COUNT(*)", "AVG(temp)", "STDDEV(temp)"))
+    Lo = plan_layout(old, _types(old))
+    assert Lo["line_ops"] == [_MA_ADD_F64, _MA_M2] and Lo["stride"] == 16
+    assert Lo["fin"] == [(0, 0, -1), (3, 2, 1), (_F_VAR_SAMP | _F_SQRT, 8, 1)]
+    assert Lo["m2desc"] == [0] * 8 + [1 | 2 << 16] + [0] * 7
+    assert "momdesc" not in Lo and "momargs" not in Lo
+    # DISTINCT forms, a boolean argument, a wrong argument count
+    for bad in ("corr(DISTINCT temp, hum)", "skewness(DISTINCT temp)", "kurtosis(DISTINCT temp)",
+                "covar_pop(DISTINCT temp, hum)", "covar_samp(DISTINCT temp, hum)", "corr(temp)", "skewness(temp, hum)"):
+        with pytest.raises(Ineligible):
+            _requests(_aggs(bad))
+    for bad in ("skewness(ok)", "kurtosis(ok)", "corr(ok, temp)", "covar_pop(temp, ok)", "covar_samp(ok, ok)"):
+        r = _requests(_aggs(bad))
+        with pytest.raises(Ineligible):
+            plan_layout(r, _types(r, ("boolean", False)))
+    # the new cap has a reason of its own; the variance cap keeps its own
+    _requests(_aggs(*[f"covar_pop(x{i}, y)" for i in range(8)]))
+    with pytest.raises(Ineligible, match="too many moment arguments"):
+        _requests(_aggs(*[f"covar_pop(x{i}, y)" for i in range(9)]))
+    with pytest.raises(Ineligible, match="too many moment arguments"):
+        _requests(_aggs(*[f"skewness(x{i})" for i in range(9)]))
+    assert MAX_VARIANCE == 8
+    with pytest.raises(Ineligible, match="too many variance arguments"):
+        _requests(_aggs(*[f"STDDEV(x{i})" for i in range(9)]))
+
+
+Q_WHOLE = ("SELECT deviceId, COUNT(*) AS c, corr(temp, hum) AS cr, covar_pop(temp, hum) AS cp, "
+           "covar_samp(temp, hum) AS cs, skewness(temp) AS sk, kurtosis(hum) AS ku, STDDEV(temp) AS sd "
+           "FROM W GROUP BY deviceId")
+_WHOLE_ITEMS = ["COUNT(*)", "corr(temp, hum)", "covar_pop(temp, hum)", "covar_samp(temp, hum)", "skewness(temp)",
+                "kurtosis(hum)", "STDDEV(temp)"]
+_WHOLE_NAMES = ["c", "cr", "cp", "cs", "sk", "ku", "sd"]
+
+
+def _whole_table():
+    """400 rows over 12 ids, plus id 77 with exactly three rows (rows 0, 1 and 2)."""
+    import numpy as np
+    rng = np.random.default_rng(41)
+    ids = rng.integers(0, 12, 403)
+    ids[:3] = 77
+    return batch(rng, 100 * S, ids)
+
+
+@pytest.mark.parametrize("nsub", [1, 2, 7])
+def test_partials_merge_to_the_whole(nsub):
+    """``local_partials`` of every row subset, concatenated, half of the parts pre-combined by ``combine_partials``,
+    then ``merge_partials`` — equal to the statement over the whole table.  One subset is empty and (from 2 subsets
+    on) one holds a single row of id 77."""
+    from dxa.engine import distagg as D
+    from dxa.engine.column import concat_tables, materialize
+    from dxa.engine.expr import Scope, evaluate
+    from dxa.sql.parser import parse_select_item
+    whole = _whole_table()
+    ctx = EvalContext(now_us=0)
+    aggs = _aggs(*_WHOLE_ITEMS)
+    assert D.decomposable(aggs, ctx)
+    assert all(D.decomposable(_aggs(one), ctx) for one in ("corr(a, b)", "covar_pop(a, b)", "covar_samp(a, b)",
+                                                           "skewness(a)", "kurtosis(a)"))
+    gx = [parse_select_item("deviceId").expr]
+    # subsets by row index: [0], the rest dealt round-robin (rows 1 and 2 of id 77 land elsewhere), and an empty one
+    n = whole.length
+    if nsub == 1:
+        subsets = [list(range(n)), []]
+    else:
+        subsets = [[0]] + [list(range(1 + k, n, nsub - 1)) for k in range(nsub - 1)] + [[]]
+    parts, meta = [], None
+    for rows in subsets:
+        sub = whole.take(torch.tensor(rows, dtype=torch.int64))
+        scope = Scope.of_table(sub, "W")
+        keys = [materialize(evaluate(g, scope, ctx)) for g in gx]
+        partial, plan, key_names = D.local_partials(gx, keys, aggs, scope, ctx)
+        parts.append(partial)
+        meta = (plan, key_names)
+    plan, key_names = meta
+    assert [sfx for _nm, sfx, _op in plan[list(aggs)[1]]] == ["sx", "sy", "m2x", "m2y", "cxy", "cnt"]
+    assert [sfx for _nm, sfx, _op in plan[list(aggs)[2]]] == ["sx", "sy", "cxy", "cnt"]
+    assert [sfx for _nm, sfx, _op in plan[list(aggs)[4]]] == ["s", "m2", "m3", "cnt"]
+    assert [sfx for _nm, sfx, _op in plan[list(aggs)[5]]] == ["s", "m2", "m3", "m4", "cnt"]
+    half = (len(parts) + 1) // 2
+    block = D.combine_partials(concat_tables(parts[:half]), plan, key_names, True)
+    got = concat_tables([block] + parts[half:])
+    out_keys, finals, ng = D.merge_partials(got, plan, key_names, aggs, True)
+    cols = {"deviceId": out_keys[0].to_pylist()}
+    for nm, ak in zip(_WHOLE_NAMES, aggs):
+        cols[nm] = finals[ak].to_pylist()
+    rows = sorted(({nm: v[i] for nm, v in cols.items()} for i in range(ng)), key=lambda r: r["deviceId"])
+    cat = Catalog()
+    cat.register("W", whole)
+    want = sorted(rows_of(run_sql(Q_WHOLE, cat, ctx)), key=lambda r: r["deviceId"])
+    SEEN["rel"] = SEEN["abs"] = SEEN["dimless"] = 0.0
+    assert_rows(rows, want, REL, ABS, DIMLESS_ABS, nsub)
+    print(f"largest deviation: relative {SEEN['rel']:.3e}, absolute {SEEN['abs']:.3e}, "
+          f"dimensionless {SEEN['dimless']:.3e}")
+
+
+def test_cpu_stream_takes_the_pane_partials():
+    """On a CPU device the statements are answered from pane partials (no dense state is created) and equal the
+    oracle; the window in which nothing passes the WHERE gives counts 0 and NULLs."""
+    store = new_store()
+
+    def each(b, q, rows):
+        if q == Q_DNONE:
+            assert rows == [{"dd": 0, "cr": None, "cs": None, "sk": None, "ci": 0}]
+
+    run_stream(churn_stream(8), [Q_ALL, Q_FIVE, Q_DGLOB, Q_DNONE, Q_MOD], torch.device("cpu"), store, each)
+    assert not dense_states(store)
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("spread", [S - 1, 3 * S])
+@pytest.mark.parametrize("block", [16, 2])
+def test_all_five_in_one_statement(gpu, monkeypatch, block, spread):
+    """The five aggregates beside the variance family and COUNT(DISTINCT kind) in one grouped statement with a
+    WHERE, NULLs in both columns, blocks of 2 panes or none, and (spread 3 S) panes clipped by the window's edge in
+    scratch slots.  Before these aggregates were decomposable the statement had no dense state at all."""
+    from dxa.engine import window_dense
+    monkeypatch.setattr(window_dense, "BLOCK", block)
+    store = new_store(win=8)
+    seen = {"blocks": 0}
+
+    def each(b, q, rows):
+        for d in dense_states(store).values():
+            if not d.disabled:
+                seen["blocks"] = max(seen["blocks"], len(d.blocks))
+
+    run_stream(stable_stream(24, True, spread), [Q_ALL], gpu, store, each)
+    d = only_state(store)
+    assert not d.disabled and d.disabled_reason is None
+    assert 4 in d.layout["line_ops"] and 3 in d.layout["line_ops"] and len(d.pairs) == 1
+    assert (seen["blocks"] > 0) == (block < 8)
+
+
+def _edge_stream(nb):
+    """Per batch: 120 rows over 20 stable ids; one row (both valid) of an id seen in that batch alone; 5 rows of ids
+    whose temp is always NULL; 6 rows of ids 8000-8002 in which temp and hum are never both non-null; 3 rows each of
+    ids 7000 and 7001 whose temp is a constant (4.0 and 9.0)."""
+    import numpy as np
+    rng = np.random.default_rng(31)
+    out = []
+    for b in range(nb):
+        ids = np.concatenate([rng.integers(0, 20, 120), [5000 + b], np.arange(9000, 9005),
+                              np.repeat(np.arange(8000, 8003), 2), [7000] * 3, [7001] * 3])
+        n = len(ids)
+        tvalid = np.concatenate([rng.random(120) > 0.1, [True], [False] * 5, [True, False] * 3, [True] * 6])
+        hvalid = np.concatenate([rng.random(120) > 0.15, [True], [True] * 5, [False, True] * 3, [True] * 6])
+        temp = (rng.integers(0, 32, n) * 0.25) ** 2
+        temp[-6:-3], temp[-3:] = 4.0, 9.0
+        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, temp=temp, temp_valid=tvalid, hum_valid=hvalid),
+                    ids))
+    return out
+
+
+@pytest.mark.gpu
+def test_edge_groups(gpu):
+    store = new_store()
+    nb = 14
+    counts = {"one": 0, "null": 0, "apart": 0, "const": 0}
+
+    def each(b, q, rows):
+        for r in rows:
+            i = r["deviceId"]
+            if i >= 9000:
+                assert r["c"] > 0 and r["n"] == 0
+                assert all(r[k] is None for k in ("cp", "cs", "cr", "sk", "ku")), r
+                counts["null"] += 1
+            elif i >= 8000:
+                assert r["n"] > 0 and all(r[k] is None for k in ("cp", "cs", "cr")), r
+                assert r["sk"] is not None and r["ku"] is not None, r
+                counts["apart"] += 1
+            elif i >= 7000:
+                assert r["n"] >= 3 and r["cp"] == 0.0 and r["cs"] == 0.0
+                assert all(math.isnan(r[k]) for k in ("cr", "sk", "ku")), r
+                counts["const"] += 1
+            elif i >= 5000:
+                assert r["c"] == 1 and r["n"] == 1 and r["cp"] == 0.0
+                assert all(math.isnan(r[k]) for k in ("cs", "cr", "sk", "ku")), r
+                counts["one"] += 1
+
+    run_stream(_edge_stream(nb), [Q_EDGE], gpu, store, each)
+    assert not only_state(store).disabled
+    assert all(v > nb for v in counts.values()), counts
+
+
+@pytest.mark.gpu
+def test_offset_values(gpu, monkeypatch):
+    """Values near 1e9 with a spread of 64, blocks of two panes: every term stays centred, so the results hold to
+    1e-6 (raw power sums would lose every digit)."""
+    from dxa.engine import window_dense
+    monkeypatch.setattr(window_dense, "BLOCK", 2)
+    store = new_store()
+    run_stream(stable_stream(14, False), [Q_OFFSET], gpu, store, rel=1e-6, dimless_abs=1e-6)
+    d = only_state(store)
+    assert not d.disabled and 4 in d.layout["line_ops"]
+
+
+@pytest.mark.gpu
+def test_rebuild_moves_op4_lines(gpu, monkeypatch):
+    """Ids drift through a 16-id dictionary that grows to 64 at most: every rebuild renumbers the op-4 line with the
+    others, and the 2-pane blocks are combined again afterwards."""
+    set_caps(monkeypatch, 16, 64, 1 << 16, 1 << 20, block=2)
+    store = new_store()
+    run_stream(churn_stream(40), [Q_FIVE], gpu, store)
+    d = only_state(store)
+    assert not d.disabled and d.disabled_reason is None
+    assert d.rebuilds > 0 and d.gcap <= 64 and 4 in d.layout["line_ops"]
+
+
+@pytest.mark.gpu
+def test_straddles_the_lds_bound(gpu, monkeypatch):
+    """Group ids on both sides of the second pass's LDS bound in one pane (two rows per id, several workgroups), and
+    a second statement whose three groups are all privatised."""
+    from dxa.engine import window_dense
+    from dxa.ops import native as N
+    import numpy as np
+    L = N.lib().dxa_win_m2_lds_groups()
+    assert L > 0
+    if L + 200 > window_dense.DENSE_GROUPS:
+        monkeypatch.setattr(window_dense, "DENSE_GROUPS", 2 * (L + 200))
+    rng = np.random.default_rng(37)
+    stream = []
+    for b in range(9):
+        ids = np.repeat(np.arange(L + 200), 2)
+        rng.shuffle(ids)
+        stream.append(((100 + b) * S, batch(rng, (100 + b) * S, ids), ids))
+    store = new_store()
+    run_stream(stream, [Q_FIVE, Q_MOD], gpu, store)
+    states = list(dense_states(store).values())
+    assert len(states) == 2 and not any(d.disabled for d in states)
+    assert all(4 in d.layout["line_ops"] for d in states)
+
+
+@pytest.mark.gpu
+def test_global_form_with_count_distinct(gpu):
+    """No GROUP BY: corr / covar_samp / skewness beside COUNT(DISTINCT deviceId), and the window in which nothing
+    passes the WHERE (counts 0, the rest NULL)."""
+    store = new_store()
+
+    def each(b, q, rows):
+        if q == Q_DNONE:
+            assert rows == [{"dd": 0, "cr": None, "cs": None, "sk": None, "ci": 0}]
+
+    run_stream(churn_stream(12), [Q_DGLOB, Q_DNONE], gpu, store, each)
+    states = list(dense_states(store).values())
+    assert len(states) == 2 and not any(d.disabled for d in states)
+    assert all(len(d.pairs) == 1 and 4 in d.layout["line_ops"] for d in states)
+
+
+@pytest.mark.gpu
+def test_partials_at_world_size_one(gpu, monkeypatch):
+    """The N-rank form at world size 1 (the patching of test_window_dense_moments.py::test_partials): the ring hands
+    ``merge_partials`` the states of ``distagg._partials``."""
+    from dxa import parallel as P
+    from dxa.engine import distagg, window_dense
+    monkeypatch.setattr(P, "active", lambda: True)
+    monkeypatch.setattr(distagg, "exchange_partials", lambda partial, key_names, grouped: (partial, P.HASHED))
+    calls = {"n": 0}
+    real = window_dense.dense_partials
+
+    def counted(*a, **k):
+        got = real(*a, **k)
+        calls["n"] += got is not None
+        return got
+
+    monkeypatch.setattr(window_dense, "dense_partials", counted)
+
+    def prepare(view):
+        view.dist = P.PARTITIONED
+
+    store = new_store()
+    stream = churn_stream(12)
+    run_stream(stream, [Q_FIVE], gpu, store, prepare=prepare)
+    d = only_state(store)
+    assert not d.disabled and d.disabled_reason is None
+    assert calls["n"] >= len(stream) - 4          # (the watermark keeps the first windows empty)
+
+
+@pytest.mark.gpu
+def test_plain_statements_have_no_op4_line(gpu):
+    store = new_store()
+    run_stream(churn_stream(12), [Q_INT, Q_SD], gpu, store)
+    states = list(dense_states(store).values())
+    assert len(states) == 2 and not any(d.disabled for d in states)
+    for d in states:
+        assert 4 not in d.layout["line_ops"] and d.momdesc_dev is None and d.momdesc_t is None
+        assert "momdesc" not in d.layout and "momargs" not in d.layout
