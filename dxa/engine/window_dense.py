@@ -62,8 +62,7 @@ A pane is accumulated in two passes: the fused multi-aggregate, which sees that 
 them 0.0, then ``win_m2_kernel``, which reads each row's group mean from the finished slot and adds the squared
 distance.  The combine merges slots with the multi-way form of Chan's update (``distagg._chan_merge``'s formula), so
 a block slot is again a valid triple and nothing is ever computed as Σx² − (Σx)²/n.  A layout without a variance
-argument has no such line and issues exactly the launches it issued before (``dxa_win_answer_m2`` /
-``dxa_win_combine_block_m2`` sit beside the plain entry points as ``dxa_win_answer_distinct`` does).  With N ranks
+argument has no such line, passes no ``m2desc`` and so runs the combine without the M2 branch (below).  With N ranks
 the partial states are ("s", "m2", "cnt"), the table ``distagg._partials`` builds.
 
 **CORR / COVAR_POP / COVAR_SAMP / SKEWNESS / KURTOSIS** (``_MOMENTS``; up to ``MAX_MOMENTS`` different arguments
@@ -78,11 +77,19 @@ unused; ``momdesc`` names per word its kind and the words it reads (count, sum, 
 ``win_mom_kernel`` fills them after the multi-aggregate (one sweep per argument or pair, all of its words at once),
 the combine merges slots with the multi-way shift formulas (window_ring.hip), and ``win_emit_kernel`` finishes them
 by Spark 2.4's rules (``fin`` entries of these kinds carry two more operand words).  A layout without one of these
-aggregates has no op-4 line, no ``momdesc`` and issues the launches it issued before (``dxa_win_answer_mom`` /
-``dxa_win_combine_block_mom`` are further siblings of the plain entry points).  The NaN rules test M2 > 0 on a
+aggregates has no op-4 line and no ``momdesc``.  The NaN rules test M2 > 0 on a
 rounded M2: equal values that are not exactly summable can give a huge number where Spark gives NaN
 (``query._moments`` has the same property).  With N ranks the partial states are those of ``distagg._partials``:
 ("s", "m2", "m3"[, "m4"], "cnt") and ("sx", "sy"[, "m2x", "m2y"], "cxy", "cnt").
+
+**One answer, one plan entry per aggregate.**  Every layout is answered by the same call, ``dxa_win_answer``
+(combine, one distinct fold per pair state, keep, compaction, output rows), and its complete blocks are combined by
+``dxa_win_combine_block``; the families differ only in what they hand over — the pair states' folds, ``m2desc``,
+``momdesc``, each 0 when the layout has none — and the absent descriptors pick the ``win_combine_kernel``
+instantiation without that branch, so a layout without X issues the launches it would issue if X did not exist
+(tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate once, where its
+slots are chosen: its ``plan`` entry, its finishing recipe and its partial states, all in slot terms; one pass after
+packing turns slots into words.  Adding an aggregate means one arm there (and, for a new kind of word, its kernels).
 """
 from __future__ import annotations
 
@@ -110,30 +117,29 @@ DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring 
 MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
 MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per statement (window_ring.hip kMaxM2Args)
 MAX_MOMENTS = 8                   # skewness / kurtosis arguments plus corr / covar pairs (window_ring.hip kMaxMomArgs)
+_ANSWER = [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p]    # ring … out_idx
+_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p]          # m2desc, its host copy, momdesc, its host copy (0: the layout has none)
 N.register_sigs({
+    "dxa_win_sizes": [N.c_p],
+    "dxa_win_emit_size": [],
     "dxa_win_pairfold_size": [],
+    "dxa_win_m2_size": [],
+    "dxa_win_m2_lds_groups": [],
+    "dxa_win_mom_size": [],
+    "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
+    "dxa_win_insert_fused": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_p, N.c_p, N.c_p],
+    "dxa_win_m2": [N.c_p, N.c_p],
+    "dxa_win_mom": [N.c_p, N.c_p],
     "dxa_win_pair_prep": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
     "dxa_win_pair_mark": [N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_i64, N.c_i32, N.c_p],
     "dxa_win_pair_or_block": [N.c_p, N.c_i64, N.c_p, N.c_i32, N.c_i32, N.c_p],
-    "dxa_win_answer_distinct": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p,
-                                N.c_p, N.c_p, N.c_p, N.c_p],
-})
-N.register_sigs({"dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p]})
-N.register_sigs({
-    "dxa_win_m2_size": [],
-    "dxa_win_m2_lds_groups": [],
-    "dxa_win_m2": [N.c_p, N.c_p],
-    "dxa_win_combine_block_m2": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p],
-    "dxa_win_answer_m2": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
-                          N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
-})
-N.register_sigs({
-    "dxa_win_mom_size": [],
-    "dxa_win_mom": [N.c_p, N.c_p],
-    "dxa_win_combine_block_mom": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p,
-                                  N.c_p, N.c_p],
-    "dxa_win_answer_mom": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
-                           N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
+    "dxa_win_combine_block": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, *_DESCS, N.c_p],
+    "dxa_win_answer": [*_ANSWER, N.c_p, N.c_p, N.c_p, *_DESCS, N.c_p],       # … emit, dictcols, folds, …, stream
+    "dxa_win_live": [*_ANSWER, N.c_p],
+    "dxa_win_remap_dict": [N.c_p, N.c_p, N.c_p, N.c_i32, N.c_p],
+    "dxa_win_remap_ring": [N.c_p, N.c_p, N.c_i32, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_p, N.c_i32,
+                           N.c_p],
+    "dxa_win_rehash": [N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p],
 })
 # the variance family → the finishing kind of its M2 word (window_ring.hip win_emit_kernel)
 _VARIANCE = {"stddev": _F_VAR_SAMP | _F_SQRT, "std": _F_VAR_SAMP | _F_SQRT, "stddev_samp": _F_VAR_SAMP | _F_SQRT,
@@ -152,21 +158,6 @@ def pair_keys(x, y):
     """The argument keys of the columns x and y of a pair (x, y) restricted to the rows where both are non-null:
     their data is the arguments', their validity ``x.valid & y.valid`` (``DenseWindow.accumulate``)."""
     return ("pair_x", x.key(), y.key()), ("pair_y", x.key(), y.key())
-
-N.register_sigs({
-    "dxa_win_live": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
-    "dxa_win_remap_dict": [N.c_p, N.c_p, N.c_p, N.c_i32, N.c_p],
-    "dxa_win_remap_ring": [N.c_p, N.c_p, N.c_i32, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_p, N.c_i32,
-                           N.c_p],
-    "dxa_win_rehash": [N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p],
-    "dxa_win_sizes": [N.c_p],
-    "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
-    "dxa_win_combine": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p],
-    "dxa_win_insert_fused": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_p, N.c_p, N.c_p],
-    "dxa_win_answer": [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p,
-                       N.c_p, N.c_p],
-    "dxa_win_emit_size": [],
-})
 
 
 class _DictCol(ctypes.Structure):
@@ -337,8 +328,9 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     ``arg_types[arg key] = (column dtype, is float64)`` of every evaluated non-distinct argument.
 
     → ``slots`` [(key, agg_multi value kind, combine op)], ``order`` (slot per word, None for padding),
-    ``line_ops`` (combine op per 8-word line), ``plan`` [(agg key, kind, slot, count slot, dtype)], ``fin`` /
-    ``pfin`` (win_emit_kernel's (kind, word, count word) per aggregate / per partial state), ``m2desc`` and
+    ``line_ops`` (combine op per 8-word line), ``plan`` [(agg key, kind, slot, count slot, dtype)] and beside it
+    ``as_f64`` (per ``plan`` entry: the finished words are doubles), ``fin`` / ``pfin`` (win_emit_kernel's (kind,
+    word, count word) per aggregate / per partial state; a distinct count has no partial), ``m2desc`` and
     ``m2args`` (the variance arguments' words for win_combine_kernel and win_m2_kernel).  With skewness / kurtosis
     / corr / covar_*: their ``fin`` entries are (kind, word, count word, operand 2, operand 3), ``momdesc`` describes
     the words of the op-4 lines to win_combine_kernel and ``momargs`` [(x key, y key or None, count, sum x, sum y,
@@ -354,20 +346,34 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         return s
 
     star = slot(("count", None), _MV_COUNT, _MA_ADD_F64)
-    plan = []
+    plan, fins, pfins, as_f64 = [], [], {}, []
     m2_of = {}                      # M2 slot → (count slot, sum slot) of the same argument
     mom_of = {}                     # M3 / M4 / Cxy slot → (kind, the slots its combine reads)
     mom_jobs = {}                   # argument key or pair keys → [x, y, count, sum x, sum y, word-0, word-1 slot]
-    mom_ops = {}                    # agg key → (operand 2 slot, operand 3 slot) of its finishing kind
-    value_only = set()              # aggregates whose partial is the value alone (distagg._partials: bool_and / bool_or)
+
+    def agg(ak, kind, s, c, dt, fkind, states, ops=(), f64=None):
+        """One aggregate, described once and in slot terms (mapped to words after packing): its ``plan`` entry, its
+        finishing recipe (emit kind, value slot, count slot[, operand slots]), its partial states {suffix: (emit
+        kind, slot, count slot)} — ``distagg._partials``' suffixes: "cnt" a count, "v" the SUM / MIN / MAX value, "s"
+        a raw double sum, "m2" / "m3" / "m4" centred sums, a pair's "sx", "sy", "cxy" (and corr's "m2x", "m2y") over
+        its both-non-null rows; None: no mergeable partial — and whether its finished words are doubles."""
+        plan.append((ak, kind, s, c, dt))
+        fins.append((fkind, s, c, *ops))
+        if states is not None:
+            pfins[ak] = states
+        as_f64.append(dt == "double" if f64 is None else f64)
+
+    def count_of(c):
+        return _F_COUNT, c, None
+
     for ak, func, arg in reqs:
         if func == "count_star":
-            plan.append((ak, "count", star, None, None))
+            agg(ak, "count", star, None, None, _F_COUNT, {"cnt": count_of(star)})
             continue
         if func == "dcount":
             # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
             # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
-            plan.append((ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None))
+            agg(ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None, _F_COUNT, None)
             continue
         if func in _PAIRED:
             # (n, Σx, Σy, Cxy) over the rows where both arguments are non-null: count and sums of the pair's masked
@@ -381,66 +387,68 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             cxy = slot(("cxy", (kx, ky)), -1, _MA_MOM)
             mom_of[cxy] = (_MOM_CXY, cnt, sx, sy)
             mom_jobs[(kx, ky)] = [kx, ky, cnt, sx, sy, cxy, None]
-            mom_ops[ak] = (None, None)
+            states = {"sx": (_F_F64, sx, cnt), "sy": (_F_F64, sy, cnt), "cxy": (_F_F64, cxy, cnt),
+                      "cnt": count_of(cnt)}
+            m2x = m2y = None
             if func == "corr":
                 m2x, m2y = slot(("m2", kx), -1, _MA_M2), slot(("m2", ky), -1, _MA_M2)
                 m2_of[m2x], m2_of[m2y] = (cnt, sx), (cnt, sy)
-                mom_ops[ak] = (m2x, m2y)
-            plan.append((ak, func, cxy, cnt, "double"))
+                states.update(m2x=(_F_F64, m2x, cnt), m2y=(_F_F64, m2y, cnt))
+            agg(ak, func, cxy, cnt, "double", _MOMENTS[func], states, (m2x, m2y))
             continue
         ck = arg.key()
         dtype, is_f = arg_types[ck]
-        if func in _MOMENTS:
-            # (n, Σx, M2, M3[, M4]) of the argument: the words AVG / STDDEV of it use and an M3 word (kurtosis: and
-            # an M4 word, whose combine reads M3) in an op-4 line
-            if dtype not in _NUMERIC:
-                raise Ineligible(f"{func} type")
-            cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
+        if func == "count_if":
+            # the predicate mask (NULL counts as false) summed as int64; never NULL, so no count word
+            cif = slot(("cif", ck), _MV_I64, _MA_ADD_U64)
+            agg(ak, "cif", cif, None, "long", _F_I64, {"cnt": (_F_I64, cif, None)})
+            continue
+        if func in (*_MOMENTS, *_VARIANCE, "sum") and dtype not in _NUMERIC:
+            raise Ineligible(f"{func} type")
+        cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
+        if func == "count":
+            agg(ak, "count", cnt, None, None, _F_COUNT, {"cnt": count_of(cnt)})
+        elif func in _MOMENTS or func in _VARIANCE:
+            # (n, Σx, M2) of the argument: the count and sum words AVG of the same argument uses, and one M2 word
+            # in a line only window_ring.hip combines (MA_M2); agg_multi leaves it at 0.0 (value kind -1) and
+            # win_m2_kernel fills it in the pane's second pass
             sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
             m2 = slot(("m2", ck), -1, _MA_M2)
             m2_of[m2] = (cnt, sm)
+            states = {"s": (_F_F64, sm, cnt), "m2": (_F_F64, m2, cnt), "cnt": count_of(cnt)}
+            if func in _VARIANCE:
+                agg(ak, func, m2, cnt, "double", _VARIANCE[func], states)
+                continue
+            # skewness / kurtosis: and an M3 word (kurtosis: and an M4 word, whose combine reads M3) in an op-4 line
             m3 = slot(("m3", ck), -1, _MA_MOM)
             mom_of[m3] = (_MOM_M3, cnt, sm, m2)
             job = mom_jobs.setdefault(ck, [ck, None, cnt, sm, None, m3, None])
             word = m3
+            states["m3"] = (_F_F64, m3, cnt)
             if func == "kurtosis":
                 word = job[6] = slot(("m4", ck), -1, _MA_MOM)
                 mom_of[word] = (_MOM_M4, cnt, sm, m2, m3)
-            mom_ops[ak] = (m2, None)
-            plan.append((ak, func, word, cnt, "double"))
-            continue
-        if func == "count_if":
-            # the predicate mask (NULL counts as false) summed as int64; never NULL, so no count word
-            plan.append((ak, "cif", slot(("cif", ck), _MV_I64, _MA_ADD_U64), None, "long"))
-            continue
-        cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
-        if func == "count":
-            plan.append((ak, "count", cnt, None, None))
-        elif func in _VARIANCE:
-            # (n, Σx, M2) of the argument: the count and sum words AVG of the same argument uses, and one M2 word
-            # in a line only window_ring.hip combines (MA_M2); agg_multi leaves it at 0.0 (value kind -1) and
-            # win_m2_kernel fills it in the pane's second pass
-            if dtype not in ("byte", "short", "int", "long", "double", "float"):
-                raise Ineligible(f"{func} type")
-            sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
-            m2 = slot(("m2", ck), -1, _MA_M2)
-            m2_of[m2] = (cnt, sm)
-            plan.append((ak, func, m2, cnt, "double"))
+                states["m4"] = (_F_F64, word, cnt)
+            agg(ak, func, word, cnt, "double", _MOMENTS[func], states, (m2, None))
         elif func in ("bmin", "bmax"):
-            # bool_and / bool_or: MIN / MAX of the argument as int64, read back as "!= 0"
-            kind = _MV_I64 | (_MV_NOT if func == "bmin" else 0)
-            value_only.add(ak)
-            plan.append((ak, "i64", slot((func[1:], ck), kind, _MA_MAX), cnt, "boolean"))
+            # bool_and / bool_or: MIN / MAX of the argument as int64, read back as "!= 0"; the partial is the value
+            # alone (distagg._partials)
+            val = slot((func[1:], ck), _MV_I64 | (_MV_NOT if func == "bmin" else 0), _MA_MAX)
+            fkind = _F_I64 | (_F_NOT if func == "bmin" else 0)
+            agg(ak, "i64", val, cnt, "boolean", fkind, {"v": (fkind, val, cnt)})
         elif func == "avg":
-            plan.append((ak, "avg", slot(("sumf", ck), _MV_F64, _MA_ADD_F64), cnt, "double"))
+            sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
+            agg(ak, "avg", sm, cnt, "double", _F_AVG, {"s": (_F_F64, sm, cnt), "cnt": count_of(cnt)})
         elif func == "sum":
-            if dtype not in ("byte", "short", "int", "long", "double", "float"):
-                raise Ineligible("sum type")
-            plan.append((ak, "sum", slot(("sum", ck), _MV_F64 if is_f else _MV_I64,
-                                         _MA_ADD_F64 if is_f else _MA_ADD_U64), cnt, "double" if is_f else "long"))
+            val = slot(("sum", ck), _MV_F64 if is_f else _MV_I64, _MA_ADD_F64 if is_f else _MA_ADD_U64)
+            fkind = _F_F64 if is_f else _F_I64
+            agg(ak, "sum", val, cnt, "double" if is_f else "long", fkind,
+                {"v": (fkind, val, cnt), "cnt": count_of(cnt)})
         else:
-            kind = (_MV_F64_ORD if is_f else _MV_I64) | (_MV_NOT if func == "min" else 0)
-            plan.append((ak, "f64" if is_f else "i64", slot((func, ck), kind, _MA_MAX), cnt, dtype))
+            val = slot((func, ck), (_MV_F64_ORD if is_f else _MV_I64) | (_MV_NOT if func == "min" else 0), _MA_MAX)
+            fkind = (_F_F64_ORD if is_f else _F_I64) | (_F_NOT if func == "min" else 0)
+            agg(ak, "f64" if is_f else "i64", val, cnt, dtype, fkind, {"v": (fkind, val, cnt), "cnt": count_of(cnt)},
+                f64=is_f)
     order, line_ops = [], []
     for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM):
         mine = [i for i, sl in enumerate(slots) if sl[2] == op]
@@ -454,55 +462,12 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     nslots = len(order)
     while nslots and order[nslots - 1] is None:
         nslots -= 1
-    fin = []
-    for ak, kind, s, c, dt in plan:
-        if kind == "count":
-            fin.append((_F_COUNT, where[s], -1))
-        elif kind == "cif":
-            fin.append((_F_I64, where[s], -1))
-        elif kind in _VARIANCE:
-            fin.append((_VARIANCE[kind], where[s], where[c]))
-        elif kind in _MOMENTS:
-            fin.append((_MOMENTS[kind], where[s], where[c], *(-1 if o is None else where[o] for o in mom_ops[ak])))
-        elif kind == "avg":
-            fin.append((_F_AVG, where[s], where[c]))
-        elif kind == "sum":
-            fin.append((_F_F64 if dt == "double" else _F_I64, where[s], where[c]))
-        else:
-            k = (_F_F64_ORD if kind == "f64" else _F_I64) | (_F_NOT if slots[s][1] & _MV_NOT else 0)
-            fin.append((k, where[s], where[c]))
-    # partial states per aggregate (distagg._partials' suffixes): "cnt" a count, "v" the SUM / MIN / MAX value,
-    # "s" AVG's and the variance family's raw double sum, "m2" the centred sum of squares; skewness / kurtosis add
-    # "m3" / "m4", a pair has "sx", "sy", "cxy" (and corr "m2x", "m2y") over its both-non-null rows
-    pfin = {}
-    for j, (ak, kind, s, c, dt) in enumerate(plan):
-        if kind == "count":
-            pfin[ak] = {"cnt": (_F_COUNT, where[s], -1)}
-        elif kind == "cif":
-            pfin[ak] = {"cnt": (_F_I64, where[s], -1)}
-        elif kind == "avg":
-            pfin[ak] = {"s": (_F_F64, where[s], where[c]), "cnt": (_F_COUNT, where[c], -1)}
-        elif kind in _VARIANCE:
-            pfin[ak] = {"s": (_F_F64, where[m2_of[s][1]], where[c]), "m2": (_F_F64, where[s], where[c]),
-                        "cnt": (_F_COUNT, where[c], -1)}
-        elif kind in _PAIRED:
-            _k, _c, sx, sy = mom_of[s]
-            pfin[ak] = {"sx": (_F_F64, where[sx], where[c]), "sy": (_F_F64, where[sy], where[c]),
-                        "cxy": (_F_F64, where[s], where[c]), "cnt": (_F_COUNT, where[c], -1)}
-            if kind == "corr":
-                pfin[ak].update(m2x=(_F_F64, where[mom_ops[ak][0]], where[c]),
-                                m2y=(_F_F64, where[mom_ops[ak][1]], where[c]))
-        elif kind in _MOMENTS:
-            m2 = mom_ops[ak][0]
-            m3 = s if kind == "skewness" else mom_of[s][4]
-            pfin[ak] = {"s": (_F_F64, where[m2_of[m2][1]], where[c]), "m2": (_F_F64, where[m2], where[c]),
-                        "m3": (_F_F64, where[m3], where[c]), "cnt": (_F_COUNT, where[c], -1)}
-            if kind == "kurtosis":
-                pfin[ak]["m4"] = (_F_F64, where[s], where[c])
-        elif ak in value_only:
-            pfin[ak] = {"v": fin[j]}
-        else:
-            pfin[ak] = {"v": fin[j], "cnt": (_F_COUNT, where[c], -1)}
+    # the recipes' slots → words (an absent count or operand: -1)
+    def words(kind, *ss):
+        return (kind, *(-1 if s is None else where[s] for s in ss))
+
+    fin = [words(*f) for f in fins]
+    pfin = {ak: {suffix: words(*f) for suffix, f in states.items()} for ak, states in pfins.items()}
     stride = 8 * len(line_ops)
     # per M2 word: its argument's count word | sum word << 16 (win_combine_kernel); the same three words per
     # variance argument for win_m2_kernel
@@ -513,7 +478,8 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         m2args.append((slots[m2][0][1], where[c], where[sm], where[m2]))
     dcount_word = {key[1]: where[i] for i, (key, _k, _o) in enumerate(slots) if key[0] == "dcount"}
     out = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
-               count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word)
+               count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word,
+               as_f64=as_f64)
     if mom_of:
         # per op-4 word: kind << 24 | the words it reads, 6 bits each (win_combine_kernel); per argument or pair the
         # words of its job in the pane's moment pass (win_mom_kernel)
@@ -749,7 +715,7 @@ class DenseWindow:
             self.m2desc_t = torch.tensor(L["m2desc"], dtype=torch.int32)
             self.m2desc_dev = self.m2desc_t.to(self.device)
         if "momdesc" in L:
-            # the op-4 combine is the M2 combine's sibling and takes both descriptors (all zero without M2 words)
+            # the combine of a layout with op-4 lines takes both descriptors (``m2desc`` all zero without M2 words)
             self.momdesc_t = torch.tensor(L["momdesc"], dtype=torch.int32)
             self.momdesc_dev = self.momdesc_t.to(self.device)
         try:
@@ -965,9 +931,7 @@ class DenseWindow:
             for k, (ck, cw, sw, mw) in enumerate(L["m2args"]):
                 d, v = xs[ck]
                 m.a[k] = _M2Arg(d.data_ptr(), 0 if v is None else v.data_ptr(), cw, sw, mw, 0)
-            m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
-            m.gcap, m.stride, m.nargs = self.gcap, self.stride, len(L["m2args"])
-            N.call("dxa_win_m2", ctypes.addressof(m), st)
+            N.call("dxa_win_m2", self._second_pass(m, len(L["m2args"]), gid, ring_ptr, n), st)
         if L.get("momargs") and n > 0:
             # and the M3 / M4 / Cxy words from the same counts and sums (win_mom_kernel): one sweep per argument or pair
             m = _MomArgs()
@@ -975,12 +939,22 @@ class DenseWindow:
                 d, v = xs[kx]
                 m.a[k] = _MomArg(d.data_ptr(), 0 if ky is None else xs[ky][0].data_ptr(),
                                  0 if v is None else v.data_ptr(), cw, sw, syw, w0, w1, 0)
-            m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
-            m.gcap, m.stride, m.nargs = self.gcap, self.stride, len(L["momargs"])
-            N.call("dxa_win_mom", ctypes.addressof(m), st)
+            N.call("dxa_win_mom", self._second_pass(m, len(L["momargs"]), gid, ring_ptr, n), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
+
+    def _descs(self):
+        """The combine's descriptors for ``dxa_win_answer`` / ``dxa_win_combine_block``: ``m2desc`` on the device and
+        on the host, ``momdesc`` likewise; 0 where the layout has none, which picks the combine without that branch."""
+        return N.ptr(self.m2desc_dev), N.ptr(self.m2desc_t), N.ptr(self.momdesc_dev), N.ptr(self.momdesc_t)
+
+    def _second_pass(self, m, nargs: int, gid: torch.Tensor, ring_ptr: int, n: int) -> int:
+        """The fields ``_M2Args`` and ``_MomArgs`` share, after their jobs: the pane's group ids and ring slot → the
+        descriptor's address."""
+        m.gid, m.row, m.n = gid.data_ptr(), ring_ptr, n
+        m.gcap, m.stride, m.nargs = self.gcap, self.stride, nargs
+        return ctypes.addressof(m)
 
     def _dev_slots(self, slots: List[int]) -> torch.Tensor:
         pin = self._pinned[self._pin_k]
@@ -1005,17 +979,8 @@ class DenseWindow:
         member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
         slots_dev = self._dev_slots(member_slots)
         st = N.stream_handle(self.device)
-        if self.momdesc_dev is not None:
-            N.call("dxa_win_combine_block_mom", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
-                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.ptr(self.m2desc_dev),
-                   self.m2desc_t.data_ptr(), N.ptr(self.momdesc_dev), self.momdesc_t.data_ptr(), st)
-        elif self.m2desc_dev is not None:
-            N.call("dxa_win_combine_block_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
-                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), N.ptr(self.m2desc_dev),
-                   self.m2desc_t.data_ptr(), st)
-        else:
-            N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev),
-                   len(member_slots), N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), st)
+        N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(member_slots),
+               N.ptr(self.line_ops_dev), dst, N.ptr(self.scal), *self._descs(), st)
         for ps in self.pairs:       # the members' presence rows ORed into the same block slot of the presence ring
             N.call("dxa_win_pair_or_block", N.ptr(ps.pres), ps.pitch, N.ptr(slots_dev), len(member_slots), dst, st)
         self.blocks[bid] = (members, dst, list(mem))
@@ -1043,29 +1008,11 @@ class DenseWindow:
                 folds.p[k] = _PairFold(ps.pres.data_ptr(), ps.pitch, ps.keys[0][2].data_ptr(), ps.scal_ptr, ps.pcap,
                                        ps.word)
             folds.n = len(self.pairs)
-        if self.momdesc_dev is not None:
-            # a layout with op-4 lines: the combine that also knows the M3 / M4 / Cxy shifts
-            N.call("dxa_win_answer_mom", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
-                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
-                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
-                   0 if folds is None else ctypes.addressof(folds), N.ptr(self.m2desc_dev),
-                   self.m2desc_t.data_ptr(), N.ptr(self.momdesc_dev), self.momdesc_t.data_ptr(), st)
-        elif self.m2desc_dev is not None:
-            # a layout with M2 lines: the combine that knows Chan's update, with or without distinct folds
-            N.call("dxa_win_answer_m2", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
-                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
-                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
-                   0 if folds is None else ctypes.addressof(folds), N.ptr(self.m2desc_dev),
-                   self.m2desc_t.data_ptr(), st)
-        elif self.pairs:
-            N.call("dxa_win_answer_distinct", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
-                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
-                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
-                   ctypes.addressof(folds), st)
-        else:
-            N.call("dxa_win_answer", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
-                   N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
-                   N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols), st)
+        # combine (the instantiation the layout's descriptors call for), folds, keep, compaction, output rows
+        N.call("dxa_win_answer", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
+               N.ptr(self.line_ops_dev), L["count_word"], N.ptr(self.scal), N.ptr(self.acc), N.ptr(self.keep),
+               N.ptr(self.out_idx), ctypes.addressof(e), ctypes.addressof(self.dictcols),
+               0 if folds is None else ctypes.addressof(folds), *self._descs(), st)
         if not defer:
             # the statement's one synchronising read
             return self._finish(self.scal.tolist(), bufs, fin, partial_proto)
@@ -1098,17 +1045,8 @@ class DenseWindow:
         okey, olen, ovalid, dst, dvalid = bufs
         if self.global_form and nout == 0:
             # no row passed the WHERE anywhere in the window: Spark's one row — counts 0, everything else NULL
-            finals = {}
-            for ak, kind, s, c, dt in L["plan"]:
-                if kind in ("count", "cif"):
-                    finals[ak] = PrimColumn("long", torch.zeros(1, dtype=torch.int64, device=self.device))
-                else:
-                    td = torch.float64 if kind in ("avg", "f64") or dt == "double" else \
-                        torch.bool if dt == "boolean" else torch.int64
-                    finals[ak] = PrimColumn("double" if kind == "avg" else dt,
-                                            torch.zeros(1, dtype=td, device=self.device),
-                                            torch.zeros(1, dtype=torch.bool, device=self.device))
-            return [], finals, 1
+            return [], self._finals([(torch.zeros(1, dtype=torch.int64, device=self.device),
+                                      torch.zeros(1, dtype=torch.bool, device=self.device)) for _ in L["plan"]]), 1
         out_keys = []
         for j, (dt, kind, vals, lens, valid) in enumerate(self.keys):
             v = ovalid[j, :nout].view(torch.bool)
@@ -1126,19 +1064,21 @@ class DenseWindow:
         cols = [(dst[r, :nout], dvalid[r, :nout].view(torch.bool)) for r in range(len(fin))]
         if partial_proto is not None:
             return self._partials(cols, out_keys, nout, *partial_proto)
+        return ([] if self.global_form else out_keys), self._finals(cols), nout
+
+    def _finals(self, cols) -> Dict:
+        """{agg key → column} from the emitted (int64 words, validity) per ``plan`` entry: a count (no count slot)
+        is a never-NULL long, everything else has the planned dtype ``dt`` over doubles (``as_f64``), booleans or the
+        words as they are."""
+        L = self.layout
         finals = {}
-        for (ak, kind, s, c, dt), (v, ok) in zip(L["plan"], cols):
-            if kind in ("count", "cif"):
+        for (ak, _kind, _s, c, dt), f64, (v, ok) in zip(L["plan"], L["as_f64"], cols):
+            if c is None:
                 finals[ak] = PrimColumn("long", v)
-            elif kind == "avg" or kind in _VARIANCE or kind in _MOMENTS:
-                finals[ak] = PrimColumn("double", v.view(torch.float64), ok)
-            elif kind == "sum":
-                finals[ak] = PrimColumn(dt, v.view(torch.float64) if dt == "double" else v, ok)
-            elif kind == "f64":
-                finals[ak] = PrimColumn(dt, v.view(torch.float64), ok)
             else:
-                finals[ak] = PrimColumn(dt, v.to(torch.bool) if dt == "boolean" else v, ok)
-        return ([] if self.global_form else out_keys), finals, nout
+                finals[ak] = PrimColumn(dt, v.view(torch.float64) if f64 else v.to(torch.bool) if dt == "boolean"
+                                        else v, ok)
+        return finals
 
     def _emit_args(self, fin):
         """The emit kernel's descriptor and this batch's output buffers ([gcap]-strided, fresh per batch: the

@@ -28,6 +28,8 @@
 // The variance family (M2) and skewness / kurtosis / corr / covar (M3, M4, Cxy) keep centred sums per pane and group:
 // second passes over the pane fill them (win_m2_kernel, win_mom_kernel) and win_combine merges slots by the multi-way
 // form of Chan's update.
+// Every layout goes through the same two host entry points, dxa_win_answer (steps 3-5) and dxa_win_combine_block; the
+// descriptors a layout passes (none, m2desc, m2desc + momdesc) pick the win_combine_kernel instantiation.
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -803,33 +805,112 @@ DXA_API int dxa_win_init(uint64_t* keys, int32_t* gid_of_slot, int64_t cap, void
   return (int)hipGetLastError();
 }
 
-// steps 5-6 + compaction: ring [R][(gcap+1)*stride] u64, slots [nslots] (device), out acc [(gcap+1)*stride],
-// keep [gcap] scratch, out_idx [gcap] (the first scal[2] entries are the kept groups, in group order)
-DXA_API int dxa_win_combine(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                            const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
-                            int64_t* out_idx, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
-                     s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc, (const int32_t*)nullptr, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
-  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
-  return (int)hipGetLastError();
+// ---- the combine and the window's answer: one entry point each, for every layout ---------------------------------
+// A layout with MA_M2 lines passes ``m2desc`` [stride] on the device (win_combine_kernel) and ``m2desc_host``, the same
+// words for the bounds check here; one with MA_MOM lines also ``momdesc`` / ``momdesc_host``, and then ``m2desc`` is
+// required too (all zero without M2 lines).  A layout without such lines passes null for both pairs.
+
+static bool m2desc_ok(const int32_t* host_desc, int32_t stride) {
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d < 0 || (d & 0xffff) >= stride || (d >> 16) >= stride) return false;
+  }
+  return true;
+}
+
+// (the word indices are 6-bit fields: no layout of more than 64 words can have MA_MOM lines)
+static bool momdesc_ok(const int32_t* host_desc, int32_t stride) {
+  if (stride > 64) return false;
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d < 0 || (d >> 24) > MOM_CXY) return false;
+    if (!d) continue;
+    for (int q = 0; q < 24; q += 6)
+      if (((d >> q) & 63) >= stride) return false;
+  }
+  return true;
+}
+
+static bool descs_ok(const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
+                     const int32_t* momdesc_host, int32_t stride) {
+  if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc)) return false;
+  return (!m2desc || m2desc_ok(m2desc_host, stride)) && (!momdesc || momdesc_ok(momdesc_host, stride));
+}
+
+static bool folds_ok(const PairFolds* pf, int32_t stride) {
+  if (!pf) return true;
+  if (pf->n < 0 || pf->n > kMaxPairStates) return false;
+  for (int k = 0; k < pf->n; ++k) {
+    const PairFold& f = pf->p[k];
+    if (f.word < 0 || f.word >= stride || (f.pitch & 15) || f.pitch < (int64_t)f.pcap + 1) return false;
+  }
+  return true;
+}
+
+// the further operand words of the kinds above F_SQRT (no other kind reads op2 / op3)
+static bool emit_ok(const EmitArgs& ea, int32_t stride) {
+  for (int r = 0; r < ea.nreq && r < kMaxEmit; ++r) {
+    const int k = ea.kind[r] & F_KIND_MASK;
+    if (k >= F_CORR && (ea.op2[r] < 0 || ea.op2[r] >= stride)) return false;
+    if (k == F_CORR && (ea.op3[r] < 0 || ea.op3[r] >= stride)) return false;
+  }
+  return true;
+}
+
+// The combine of ``slots`` into ``out`` with the instantiation the (checked) descriptors call for: the per-batch form
+// over the groups in use, or (kBlock) the block form that writes all gcap + 1 rows.
+template <bool kBlock>
+static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t stride, const int32_t* slots,
+                           int32_t nslots, const int32_t* line_op, const int32_t* scal, unsigned long long* out,
+                           const int32_t* m2desc, const int32_t* momdesc, hipStream_t s) {
+  const int32_t rows = kBlock ? gcap + 1 : gcap;
+  auto kernel = momdesc  ? win_combine_kernel<kBlock, true, true>
+                : m2desc ? win_combine_kernel<kBlock, true, false>
+                         : win_combine_kernel<kBlock, false, false>;
+  hipLaunchKernelGGL(kernel, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s, ring,
+                     (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap, kBlock ? rows : 0, out,
+                     m2desc, momdesc);
 }
 
 // a block of ring slots pre-combined into another ring slot (every row is written, so groups the dictionary gains
 // later read the identity there; the members are read only for the scal[0] groups in use): out = ring slot ``dst``
 DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                                  const int32_t* line_op, int32_t dst, const int32_t* scal, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
+                                  const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
+                                  const int32_t* m2desc_host, const int32_t* momdesc, const int32_t* momdesc_host,
+                                  void* st) {
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, stride)) return (int)hipErrorInvalidValue;
   unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL((win_combine_kernel<true, false, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
-                     dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, gcap + 1, r + (int64_t)dst * slot_words, (const int32_t*)nullptr, (const int32_t*)nullptr);
+  launch_combine<true>(r, gcap, stride, slots, nslots, line_op, scal, r + (int64_t)dst * (gcap + 1) * stride, m2desc,
+                       momdesc, (hipStream_t)st);
+  return (int)hipGetLastError();
+}
+
+// The window's answer: ring [R][(gcap+1)*stride] u64, slots [nslots] (device) → acc [(gcap+1)*stride] the combined
+// rows, keep [gcap] scratch, out_idx [gcap] (the first scal[2] entries are the kept groups, in group order).
+// Steps 5-6: the combine, one distinct fold per pair state of ``folds`` (may be null) into the combined rows, keep,
+// compaction, and — unless ``emit`` is null — the output rows by position (win_emit_kernel).
+DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
+                           const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
+                           int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
+                           const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
+                           const int32_t* momdesc_host, void* st) {
+  hipStream_t s = (hipStream_t)st;
+  const EmitArgs* ea = (const EmitArgs*)emit;
+  const PairFolds* pf = (const PairFolds*)folds;
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, stride) || !folds_ok(pf, stride) ||
+      (ea && (!dictcols || !emit_ok(*ea, stride))))
+    return (int)hipErrorInvalidValue;
+  hipMemsetAsync(scal + 2, 0, 4, s);
+  launch_combine<false>((const unsigned long long*)ring, gcap, stride, slots, nslots, line_op, scal,
+                        (unsigned long long*)acc, m2desc, momdesc, s);
+  for (int k = 0; pf && k < pf->n; ++k)
+    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf->p[k].pcap + 15) >> 4, 256, 256 * 8)),
+                       dim3(256), 0, s, pf->p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
+                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
+  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
+  if (ea) hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *ea,
+                             *(const DictCols*)dictcols);
   return (int)hipGetLastError();
 }
 
@@ -837,12 +918,14 @@ DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, cons
 // last clean status, finds the groups that still have rows in the panes it holds (dxa_win_live), and renumbers them
 // densely: old id out_idx[p] becomes p, p < live.  Off the hot path (once per ~capacity / 2 new keys at the least).
 
-// The live groups of the given pane slots: the window combine, keep and compact passes over those slots →
+// The live groups of the given pane slots: the answer's combine, keep and compact passes over those slots, without
+// descriptors whatever the layout (only the combined count word is read afterwards) and without output rows →
 // out_idx[0 .. scal[2]) = the old ids with COUNT(*) > 0 there, increasing.
 DXA_API int dxa_win_live(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
                          const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
                          int64_t* out_idx, void* st) {
-  return dxa_win_combine(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, st);
+  return dxa_win_answer(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 // The dictionary's key columns into fresh ones (``dst`` is zero-filled; earlier batches' output strings are views of
@@ -908,19 +991,7 @@ DXA_API int dxa_win_insert_fused(const void* keycols, const void* dictcols, cons
   return (int)hipGetLastError();
 }
 
-// steps 5-6, compaction and the output rows by position (win_emit_kernel)
-DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                           const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
-                           int64_t* out_idx, const void* emit, const void* dictcols, void* st) {
-  const int rc = dxa_win_combine(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx,
-                                 st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, (hipStream_t)st,
-                     *(const EmitArgs*)emit, *(const DictCols*)dictcols);
-  return (int)hipGetLastError();
-}
-
-// ---- COUNT(DISTINCT x): entry points -----------------------------------------------------------------------------
+// ---- COUNT(DISTINCT x): entry points (the folds themselves are launched by dxa_win_answer) ------------------------
 
 DXA_API int dxa_win_pairfold_size() { return (int)sizeof(PairFolds); }
 
@@ -954,35 +1025,7 @@ DXA_API int dxa_win_pair_or_block(uint8_t* pres, int64_t pitch, const int32_t* s
   return (int)hipGetLastError();
 }
 
-// dxa_win_answer for a statement with distinct counts: combine, the distinct folds into the combined rows, then keep,
-// compaction and the output rows
-DXA_API int dxa_win_answer_distinct(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots,
-                                    int32_t nslots, const int32_t* line_op, int32_t count_word, int32_t* scal,
-                                    void* acc, uint8_t* keep, int64_t* out_idx, const void* emit,
-                                    const void* dictcols, const void* folds, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  const PairFolds& pf = *(const PairFolds*)folds;
-  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
-  for (int k = 0; k < pf.n; ++k)
-    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
-      return (int)hipErrorInvalidValue;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, false, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)), dim3(256), 0,
-                     s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal, gcap, 0,
-                     (unsigned long long*)acc, (const int32_t*)nullptr, (const int32_t*)nullptr);
-  for (int k = 0; k < pf.n; ++k)
-    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
-                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
-  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
-  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
-  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *(const EmitArgs*)emit,
-                     *(const DictCols*)dictcols);
-  return (int)hipGetLastError();
-}
-
-// ---- STDDEV / VARIANCE: entry points -----------------------------------------------------------------------------
+// ---- STDDEV / VARIANCE: the pane's second pass (the combine is dxa_win_answer's and dxa_win_combine_block's) -------
 
 DXA_API int dxa_win_m2_size() { return (int)sizeof(M2Args); }
 
@@ -1004,59 +1047,7 @@ DXA_API int dxa_win_m2(const void* args, void* st) {
   return (int)hipGetLastError();
 }
 
-static bool m2desc_ok(const int32_t* host_desc, int32_t stride) {
-  for (int w = 0; w < stride; ++w) {
-    const int32_t d = host_desc[w];
-    if (d < 0 || (d & 0xffff) >= stride || (d >> 16) >= stride) return false;
-  }
-  return true;
-}
-
-// dxa_win_combine_block for a layout with M2 lines.  ``m2desc`` [stride] on the device (win_combine_kernel),
-// ``m2desc_host`` the same words for the bounds check.
-DXA_API int dxa_win_combine_block_m2(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                                     const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
-                                     const int32_t* m2desc_host, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride)) return (int)hipErrorInvalidValue;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL((win_combine_kernel<true, true, false>), dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)),
-                     dim3(256), 0, s, (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, gcap + 1, r + (int64_t)dst * slot_words, m2desc, (const int32_t*)nullptr);
-  return (int)hipGetLastError();
-}
-
-// dxa_win_answer / dxa_win_answer_distinct for a layout with M2 lines (``folds`` may be null: no distinct counts)
-DXA_API int dxa_win_answer_m2(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                              const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
-                              int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
-                              const int32_t* m2desc, const int32_t* m2desc_host, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride)) return (int)hipErrorInvalidValue;
-  PairFolds none{};
-  const PairFolds& pf = folds ? *(const PairFolds*)folds : none;
-  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
-  for (int k = 0; k < pf.n; ++k)
-    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
-      return (int)hipErrorInvalidValue;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, true, false>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
-                     dim3(256), 0, s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, 0, (unsigned long long*)acc, m2desc, (const int32_t*)nullptr);
-  for (int k = 0; k < pf.n; ++k)
-    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
-                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
-  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
-  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
-  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, *(const EmitArgs*)emit,
-                     *(const DictCols*)dictcols);
-  return (int)hipGetLastError();
-}
-
-// ---- CORR / COVAR / SKEWNESS / KURTOSIS: entry points -------------------------------------------------------------
+// ---- CORR / COVAR / SKEWNESS / KURTOSIS: the pane's moment pass -----------------------------------------------------
 
 DXA_API int dxa_win_mom_size() { return (int)sizeof(MomArgs); }
 
@@ -1072,72 +1063,5 @@ DXA_API int dxa_win_mom(const void* args, void* st) {
   }
   if (m.n <= 0 || m.nargs == 0) return 0;
   hipLaunchKernelGGL(win_mom_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
-  return (int)hipGetLastError();
-}
-
-static bool momdesc_ok(const int32_t* host_desc, int32_t stride) {
-  for (int w = 0; w < stride; ++w) {
-    const int32_t d = host_desc[w];
-    if (d < 0 || (d >> 24) > MOM_CXY) return false;
-    if (!d) continue;
-    for (int q = 0; q < 24; q += 6)
-      if (((d >> q) & 63) >= stride) return false;
-  }
-  return true;
-}
-
-// dxa_win_combine_block_m2 for a layout that also has MA_MOM lines (``m2desc`` is all zero without M2 lines)
-DXA_API int dxa_win_combine_block_mom(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                                      const int32_t* line_op, int32_t dst, const int32_t* scal,
-                                      const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
-                                      const int32_t* momdesc_host, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride) || !momdesc || !momdesc_host ||
-      !momdesc_ok(momdesc_host, stride) || stride > 64)
-    return (int)hipErrorInvalidValue;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  unsigned long long* r = (unsigned long long*)ring;
-  hipLaunchKernelGGL((win_combine_kernel<true, true, true>),
-                     dim3(dxa_blocks((int64_t)(gcap + 1) * stride, 256, 256 * 64)), dim3(256), 0, s,
-                     (const unsigned long long*)r, slot_words, slots, nslots, stride, line_op, scal, gcap, gcap + 1,
-                     r + (int64_t)dst * slot_words, m2desc, momdesc);
-  return (int)hipGetLastError();
-}
-
-// dxa_win_answer_m2 for a layout that also has MA_MOM lines (``folds`` may be null: no distinct counts)
-DXA_API int dxa_win_answer_mom(const void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
-                               const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
-                               int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
-                               const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
-                               const int32_t* momdesc_host, void* st) {
-  hipStream_t s = (hipStream_t)st;
-  if (!m2desc || !m2desc_host || !m2desc_ok(m2desc_host, stride) || !momdesc || !momdesc_host ||
-      !momdesc_ok(momdesc_host, stride) || stride > 64)
-    return (int)hipErrorInvalidValue;
-  const EmitArgs& ea = *(const EmitArgs*)emit;
-  for (int r = 0; r < ea.nreq && r < kMaxEmit; ++r)
-    if ((ea.kind[r] & F_KIND_MASK) >= F_COVAR_POP &&
-        (((ea.kind[r] & F_KIND_MASK) >= F_CORR && (ea.op2[r] < 0 || ea.op2[r] >= stride)) ||
-         ((ea.kind[r] & F_KIND_MASK) == F_CORR && (ea.op3[r] < 0 || ea.op3[r] >= stride))))
-      return (int)hipErrorInvalidValue;
-  PairFolds none{};
-  const PairFolds& pf = folds ? *(const PairFolds*)folds : none;
-  if (pf.n < 0 || pf.n > kMaxPairStates) return (int)hipErrorInvalidValue;
-  for (int k = 0; k < pf.n; ++k)
-    if (pf.p[k].word < 0 || pf.p[k].word >= stride || (pf.p[k].pitch & 15) || pf.p[k].pitch < (int64_t)pf.p[k].pcap + 1)
-      return (int)hipErrorInvalidValue;
-  const int64_t slot_words = (int64_t)(gcap + 1) * stride;
-  hipMemsetAsync(scal + 2, 0, 4, s);
-  hipLaunchKernelGGL((win_combine_kernel<false, true, true>), dim3(dxa_blocks((int64_t)gcap * stride, 256, 256 * 64)),
-                     dim3(256), 0, s, (const unsigned long long*)ring, slot_words, slots, nslots, stride, line_op, scal,
-                     gcap, 0, (unsigned long long*)acc, m2desc, momdesc);
-  for (int k = 0; k < pf.n; ++k)
-    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf.p[k].pcap + 15) >> 4, 256, 256 * 8)),
-                       dim3(256), 0, s, pf.p[k], slots, nslots, scal, gcap, (double*)acc, stride);
-  hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
-                     (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
-  hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
-  hipLaunchKernelGGL(win_emit_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s, ea,
-                     *(const DictCols*)dictcols);
   return (int)hipGetLastError();
 }

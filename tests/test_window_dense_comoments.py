@@ -297,6 +297,56 @@ def test_layout_of_the_comoment_aggregates():
         _requests(_aggs(*[f"STDDEV(x{i})" for i in range(9)]))
 
 
+def _call_text(name):
+    """A call of the supported aggregate ``name`` over the columns of ``batch``."""
+    from dxa.engine.window_dense import _BOOL, _PAIRED
+    arg = "temp, hum" if name in _PAIRED else "temp > 8" if name in _BOOL or name == "count_if" else "temp"
+    return f"{name}({arg})"
+
+
+def test_partial_states_are_those_of_local_partials():
+    """For every supported aggregate ``plan_layout``'s ``pfin`` holds exactly the suffixes that
+    ``distagg.local_partials`` plans for the call (over an empty CPU table, as ``dense_partials`` builds its
+    prototype), so ``_partial_spec`` finds a word for every partial column and carries no other.  COUNT(DISTINCT x)
+    is not decomposable and has no entry in ``pfin`` at all."""
+    from dxa.engine import distagg as D
+    from dxa.engine.column import ConstColumn, materialize
+    from dxa.engine.expr import Scope, evaluate
+    from dxa.engine.window_dense import _SUPPORTED, _requests, plan_layout
+    from dxa.sql.parser import parse_select_item
+    import numpy as np
+    empty = batch(np.random.default_rng(0), 100 * S, np.arange(4)).take(torch.empty(0, dtype=torch.int64))
+    ctx = EvalContext(now_us=0)
+    scope = Scope.of_table(empty, "W")
+    gx = [parse_select_item("deviceId").expr]
+    keys = [materialize(evaluate(g, scope, ctx)) for g in gx]
+
+    def layout(aggs):
+        reqs = _requests(aggs)
+        types = {}
+        for _, f, arg in reqs:
+            for a in arg if isinstance(arg, tuple) else () if arg is None or f == "dcount" else (arg,):
+                c = evaluate(a, scope, ctx)
+                c = c.materialize() if isinstance(c, ConstColumn) else c
+                types[a.key()] = (c.dtype, c.data.dtype == torch.float64)
+        return plan_layout(reqs, types)
+
+    for text in ["COUNT(*)"] + [_call_text(name) for name in sorted(_SUPPORTED)]:
+        aggs = _aggs(text)
+        (ak,) = aggs
+        assert D.decomposable(aggs, ctx), text
+        _partial, plan, _key_names = D.local_partials(gx, keys, aggs, scope, ctx)
+        suffixes = [sfx for _nm, sfx, _op in plan[ak]]
+        assert len(set(suffixes)) == len(suffixes) > 0, text
+        assert set(layout(aggs)["pfin"][ak]) == set(suffixes), (text, suffixes)
+    for text in ("COUNT(DISTINCT temp)", "COUNT(DISTINCT kind)"):
+        aggs = _aggs("AVG(temp)", text)
+        avg, dc = aggs
+        assert not D.decomposable(aggs, ctx) and aggs[dc].distinct
+        L = layout(aggs)
+        assert set(L["pfin"]) == {avg} and L["dcount_word"], text
+
+
 Q_WHOLE = ("SELECT deviceId, COUNT(*) AS c, corr(temp, hum) AS cr, covar_pop(temp, hum) AS cp, "
            "covar_samp(temp, hum) AS cs, skewness(temp) AS sk, kurtosis(hum) AS ku, STDDEV(temp) AS sd "
            "FROM W GROUP BY deviceId")
@@ -557,3 +607,82 @@ def test_plain_statements_have_no_op4_line(gpu):
     for d in states:
         assert 4 not in d.layout["line_ops"] and d.momdesc_dev is None and d.momdesc_t is None
         assert "momdesc" not in d.layout and "momargs" not in d.layout
+
+
+# ---- one answer entry point: the dispatch arms and the launch sequences ---------------------------------------------
+Q_CP = "SELECT deviceId, covar_pop(temp, hum) AS cp FROM W GROUP BY deviceId"
+Q_CP_GLOB = "SELECT COUNT(DISTINCT deviceId) AS dd, covar_pop(temp, hum) AS cp FROM W"
+Q_SK = "SELECT deviceId, skewness(temp) AS sk FROM W GROUP BY deviceId"
+Q_DC = "SELECT deviceId, COUNT(*) AS c, COUNT(DISTINCT kind) AS dk FROM W GROUP BY deviceId"
+
+
+def small_stream(nb, mid_pane=False, groups=4, rows=40):
+    """40 rows per batch over 4 ids.  ``mid_pane``: event times in the middle half of the batch's second, so a pane is
+    wholly inside a window or wholly outside it (none is clipped into a scratch slot) and exactly one pane enters
+    the window per batch."""
+    import numpy as np
+    rng = np.random.default_rng(43)
+    out = []
+    for b in range(nb):
+        ids = rng.integers(0, groups, rows)
+        T = (100 + b) * S
+        out.append((T, batch(rng, T - S // 4, ids, S // 2) if mid_pane else batch(rng, T, ids), ids))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("q", [Q_CP, Q_CP_GLOB])
+def test_covar_pop_alone(gpu, monkeypatch, q):
+    """An op-4 line and no M2 line: ``momdesc`` beside an all-zero ``m2desc``, through the per-batch combine and the
+    2-pane block combine; grouped, and in global form beside COUNT(DISTINCT deviceId)."""
+    from dxa.engine import window_dense
+    monkeypatch.setattr(window_dense, "BLOCK", 2)
+    store = new_store()
+    seen = {"blocks": 0}
+
+    def each(b, _q, rows):
+        for d in dense_states(store).values():
+            seen["blocks"] = max(seen["blocks"], len(d.blocks))
+
+    run_stream(small_stream(14), [q], gpu, store, each)
+    d = only_state(store)
+    assert not d.disabled and d.disabled_reason is None
+    assert d.momdesc_dev is not None and d.m2desc_dev is not None and not any(d.layout["m2desc"])
+    assert 4 in d.layout["line_ops"] and 3 not in d.layout["line_ops"]
+    assert len(d.pairs) == (q == Q_CP_GLOB) and seen["blocks"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("q,second_pass,pairs", [(Q_INT, [], 0), (Q_SD, ["dxa_win_m2"], 0),
+                                                 (Q_SK, ["dxa_win_m2", "dxa_win_mom"], 0), (Q_DC, [], 1)])
+def test_entry_points_per_steady_state_batch(gpu, monkeypatch, q, second_pass, pairs):
+    """The native entry points of a batch in which one pane enters the window and nothing is rebuilt: the group
+    insert, the multi-aggregate, the second passes the layout has, per pair state its insert, then — on a batch that
+    completes a 2-pane block — one block combine and one presence OR per pair state, then the one answer.  A layout
+    without a family issues none of its launches."""
+    from dxa.engine import window_dense
+    from launch_count import count_launches
+    monkeypatch.setattr(window_dense, "BLOCK", 2)
+    store = new_store()
+    pane = ["dxa_win_insert_fused", "dxa_aggregate_multi", *second_pass,
+            *["dxa_win_pair_prep", "dxa_win_insert_fused", "dxa_win_pair_mark"] * pairs]
+    block = ["dxa_win_combine_block", *["dxa_win_pair_or_block"] * pairs]
+    completed_seen = set()
+    for b, (T, tbl, _ids) in enumerate(small_stream(14, mid_pane=True)):
+        views, _ = store.process(tbl.to(gpu), T, S)
+        cat = Catalog()
+        cat.register("W", views["W"])
+        states = list(dense_states(store).values())
+        before = set(states[0].blocks) if states else set()
+        with count_launches() as log:
+            out = run_sql(q, cat, EvalContext(now_us=0, device=gpu))
+        assert_rows(rows_of(out), oracle(q, views["W"]), REL, ABS, DIMLESS_ABS, (b, q))
+        if b < 8:                                   # the watermark and the 6-pane window: full from batch 7 on
+            continue
+        d = only_state(store)
+        assert not d.disabled and d.rebuilds == 0 and len(d.pairs) == pairs
+        completed = len(set(d.blocks) - before)
+        completed_seen.add(completed)
+        native = [nm for nm in log if nm.startswith("dxa_")]
+        assert native == pane + block * completed + ["dxa_win_answer"], (b, native)
+    assert completed_seen == {0, 1}
