@@ -15,9 +15,9 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
   compacts them; the host reads one 12-byte status (groups, collisions, output rows) — the statement's only
   synchronisation — and builds the output columns as views of the dictionary and the finished aggregates.
 
-Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over non-decimal numeric,
-boolean or timestamp arguments (and COUNT(DISTINCT x), the variance family and corr / covar_pop / covar_samp /
-skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some), with plain key columns,
+Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over numeric (decimals
+included, below), boolean or timestamp arguments (and COUNT(DISTINCT x), the variance family and corr / covar_pop /
+covar_samp / skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some), with plain key columns,
 deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
 exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
@@ -82,10 +82,38 @@ rounded M2: equal values that are not exactly summable can give a huge number wh
 (``query._moments`` has the same property).  With N ranks the partial states are those of ``distagg._partials``:
 ("s", "m2", "m3"[, "m4"], "cnt") and ("sx", "sy"[, "m2x", "m2y"], "cxy", "cnt").
 
+**Exact decimals** (an unsuffixed fractional literal is a decimal and a JSON integer a long, so ``AVG(temp * 1.8 +
+32)`` has a decimal argument).  SUM(x) and AVG(x) of ``decimal(p, s)``, p ≤ ``SUM_PRECISION`` = 28, one int64 lane
+per row or two, keep three words per pane and group: w0 = Σ (lo & 0xffffffff), w1 = Σ (lo >> 32) (unsigned) and
+w2 = Σ hi (signed; ``x >> 63`` of a one-lane value), shared by SUM and AVG of one argument with its count word.
+Each word is exact below 2^31 rows per group in the window, and then the total is below 10^28 · 2^31 < 10^38: it
+cannot overflow the p + 10 digits of SUM's type, so no ``fits`` test is needed (p > 28, where Spark caps the sum
+type at 38 digits, overflow-to-NULL matters and a 128-bit total can wrap, stays on the paned path: "decimal
+precision").  The words sit in ordinary ``MA_ADD_U64`` lines: the combine, block slots, rebuild and remap treat them
+as plain u64 sums; agg_multi sees them as unused (value kind -1) and leaves them 0, and ``win_dec_kernel`` — one
+launch per accumulated pane for all decimal jobs of the statement, after the multi-aggregate — reads the decimal
+column in place (a pointer and a lane stride of 1 or 2) and adds the limbs, ids below the LDS bound in LDS u64
+arrays, the others with 64-bit global atomics.  Integer adds: the result does not depend on the arrival order.
+``win_emit_kernel`` reassembles (lo, hi) with carries and, for AVG, divides the 128-bit magnitude exactly by the
+count (32-bit schoolbook division, HALF_UP on the magnitude, the sign afterwards — ``decimal.avg_from_sum``'s
+result without its host loop); a decimal result takes two output rows, packed per result type by ``decimal.pack``.
+MIN / MAX of a one-lane decimal is the int64 slot with a decimal dtype.  Of a two-lane decimal it is a two-word
+order key: the hi lane in an ``MA_MAX`` slot (``MV_NOT`` for MIN) filled by agg_multi from a contiguous copy of the
+lane, and the lo lane's key (unsigned order mapped to signed, complemented for MIN) in a line of one more combine
+op (``MA_LOKEY`` = 5) that agg_multi sees as an unused ``MA_MAX`` line (INT64_MIN); a second job kind of
+``win_dec_kernel`` takes the max of the lo keys of the rows whose hi key equals the slot's finished hi word, and the
+combine the max of the lo words over the slots whose hi word equals the max hi (``lodesc`` names each lo word's hi
+word), so all-identity rows stay the identity.  COUNT and count_if over a decimal read its validity or the
+predicate; the variance and moment families take ``decimal.to_double`` of it (as ``distagg._as_double`` does).  The
+results have the paned path's types — SUM ``decimal(p + 10, s)``, AVG ``decimal(p + 4, s + 4)``, MIN / MAX the
+argument's — and the partial states are ``distagg._partials``': SUM ("v" of the sum type, "cnt"), AVG
+("davg_{p}_{s}" — the sum —, "cnt"), MIN / MAX ("v", "cnt").  Decimal group keys and COUNT(DISTINCT decimal)
+remain ineligible ("key type", "argument type").
+
 **One answer, one plan entry per aggregate.**  Every layout is answered by the same call, ``dxa_win_answer``
 (combine, one distinct fold per pair state, keep, compaction, output rows), and its complete blocks are combined by
 ``dxa_win_combine_block``; the families differ only in what they hand over — the pair states' folds, ``m2desc``,
-``momdesc``, each 0 when the layout has none — and the absent descriptors pick the ``win_combine_kernel``
+``momdesc``, ``lodesc``, each 0 when the layout has none — and the absent descriptors pick the ``win_combine_kernel``
 instantiation without that branch, so a layout without X issues the launches it would issue if X did not exist
 (tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate once, where its
 slots are chosen: its ``plan`` entry, its finishing recipe and its partial states, all in slot terms; one pass after
@@ -100,11 +128,13 @@ from typing import Dict, List, Optional
 import torch
 
 from ..ops import native as N
-from ..ops.groupby import (_F_AVG, _F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP, _F_F64, _F_F64_ORD, _F_I64,
-                           _F_KURT, _F_NOT, _F_SKEW, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64,
-                           _MA_M2, _MA_MAX, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT, _MV_F64, _MV_F64_ORD,
-                           _MV_I64, _MV_NOT)
+from ..ops.groupby import (_DEC_KEY_MAX, _DEC_KEY_MIN, _DEC_SUM, _F_AVG, _F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP,
+                           _F_DEC_AVG, _F_DEC_MM, _F_DEC_SUM, _F_F64, _F_F64_ORD, _F_HI, _F_I64, _F_KURT, _F_NOT,
+                           _F_SKEW, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64, _MA_LOKEY, _MA_M2,
+                           _MA_MAX, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64,
+                           _MV_NOT)
 from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
+from . import decimal as Dec
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
 from .decimal import is_decimal
 
@@ -117,8 +147,11 @@ DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring 
 MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
 MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per statement (window_ring.hip kMaxM2Args)
 MAX_MOMENTS = 8                   # skewness / kurtosis arguments plus corr / covar pairs (window_ring.hip kMaxMomArgs)
+MAX_DECIMAL = 8                   # decimal sum arguments plus two-lane decimal MIN / MAX (window_ring.hip kMaxDecJobs)
+SUM_PRECISION = 28                # SUM / AVG of decimal(p, s) is answered here for p up to this (``plan_layout``)
 _ANSWER = [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p]    # ring … out_idx
-_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p]          # m2desc, its host copy, momdesc, its host copy (0: the layout has none)
+# m2desc, its host copy, momdesc, its host copy, lodesc, its host copy (0: the layout has none)
+_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p]
 N.register_sigs({
     "dxa_win_sizes": [N.c_p],
     "dxa_win_emit_size": [],
@@ -126,6 +159,8 @@ N.register_sigs({
     "dxa_win_m2_size": [],
     "dxa_win_m2_lds_groups": [],
     "dxa_win_mom_size": [],
+    "dxa_win_dec_size": [],
+    "dxa_win_dec": [N.c_p, N.c_p],
     "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
     "dxa_win_insert_fused": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_p, N.c_p, N.c_p],
     "dxa_win_m2": [N.c_p, N.c_p],
@@ -210,6 +245,18 @@ class _MomArgs(ctypes.Structure):
                 ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class _DecJob(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("lanes", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("w0", ctypes.c_int32), ("w1", ctypes.c_int32), ("w2", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+class _DecArgs(ctypes.Structure):
+    _fields_ = [("a", _DecJob * MAX_DECIMAL), ("gid", ctypes.c_void_p), ("row", ctypes.c_void_p),
+                ("n", ctypes.c_int64), ("gcap", ctypes.c_int32), ("stride", ctypes.c_int32),
+                ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -223,7 +270,8 @@ def _sizes() -> List[int]:
                 N.lib().dxa_win_emit_size() != ctypes.sizeof(_EmitArgs) or \
                 N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds) or \
                 N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args) or \
-                N.lib().dxa_win_mom_size() != ctypes.sizeof(_MomArgs):
+                N.lib().dxa_win_mom_size() != ctypes.sizeof(_MomArgs) or \
+                N.lib().dxa_win_dec_size() != ctypes.sizeof(_DecArgs):
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
@@ -334,7 +382,21 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     ``m2args`` (the variance arguments' words for win_combine_kernel and win_m2_kernel).  With skewness / kurtosis
     / corr / covar_*: their ``fin`` entries are (kind, word, count word, operand 2, operand 3), ``momdesc`` describes
     the words of the op-4 lines to win_combine_kernel and ``momargs`` [(x key, y key or None, count, sum x, sum y,
-    word 0, word 1)] lists win_mom_kernel's jobs; a pair's slots are keyed by ``pair_keys``."""
+    word 0, word 1)] lists win_mom_kernel's jobs; a pair's slots are keyed by ``pair_keys``.
+
+    A decimal argument's ``arg_types`` entry carries its ``DecimalType``.  SUM / AVG of decimal(p, s), p ≤
+    ``SUM_PRECISION``, share three limb-sum slots per argument — Σ (lo & 0xffffffff), Σ (lo >> 32), Σ hi, in
+    ``MA_ADD_U64`` lines with value kind -1 — and its count slot.  Each limb sum is exact while a group has fewer than
+    2^31 rows in the window, and then the total is below 10^28 · 2^31 < 10^38: it cannot overflow the p + 10 digits
+    of SUM's type (nor 128 bits), so unlike the paned path's ``decimal.agg_sum`` no ``fits`` test is needed.  Beyond
+    28 digits Spark's sum type is capped at 38, overflow-to-NULL matters and the total can wrap: "decimal precision".
+    MIN / MAX of a narrow decimal is the int64 slot with a decimal dtype; of a two-lane one a two-word order key, the
+    hi lane in an ``MA_MAX`` slot and the lo lane's key in a slot of an ``MA_LOKEY`` line (``lodesc``: per such word
+    its high word | 1 << 16).  A decimal result takes two ``fin`` rows (lo, then hi with ``_F_HI``), so ``rows`` gives
+    per ``plan`` entry (first ``fin`` row, rows), and a decimal partial state in ``pfin`` is a list of two recipes.
+    ``decargs`` [(arg key, job kind, word 0, word 1, word 2)] lists win_dec_kernel's jobs.  ``lodesc`` / ``decargs``
+    are absent from a layout without such words.  The variance and moment families take a decimal argument as the
+    double ``decimal.to_double`` gives (as Spark casts it)."""
     # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
     slots, keyed = [], {}
 
@@ -346,7 +408,9 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         return s
 
     star = slot(("count", None), _MV_COUNT, _MA_ADD_F64)
-    plan, fins, pfins, as_f64 = [], [], {}, []
+    plan, fins, pfins, as_f64, rows = [], [], {}, [], []
+    lo_of = {}                      # low key slot of a two-lane decimal MIN / MAX → its high key slot
+    dec_jobs = {}                   # (job, argument key) → (argument key, win_dec_kernel job kind, its three slots)
     m2_of = {}                      # M2 slot → (count slot, sum slot) of the same argument
     mom_of = {}                     # M3 / M4 / Cxy slot → (kind, the slots its combine reads)
     mom_jobs = {}                   # argument key or pair keys → [x, y, count, sum x, sum y, word-0, word-1 slot]
@@ -356,15 +420,25 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         finishing recipe (emit kind, value slot, count slot[, operand slots]), its partial states {suffix: (emit
         kind, slot, count slot)} — ``distagg._partials``' suffixes: "cnt" a count, "v" the SUM / MIN / MAX value, "s"
         a raw double sum, "m2" / "m3" / "m4" centred sums, a pair's "sx", "sy", "cxy" (and corr's "m2x", "m2y") over
-        its both-non-null rows; None: no mergeable partial — and whether its finished words are doubles."""
+        its both-non-null rows; None: no mergeable partial — and whether its finished words are doubles.  ``fkind``
+        may be a list of two whole recipes instead (``two``: a 128-bit result), and so may a partial state."""
         plan.append((ak, kind, s, c, dt))
-        fins.append((fkind, s, c, *ops))
+        recipes = fkind if isinstance(fkind, list) else [(fkind, s, c, *ops)]
+        rows.append((len(fins), len(recipes)))
+        fins.extend(recipes)
         if states is not None:
             pfins[ak] = states
         as_f64.append(dt == "double" if f64 is None else f64)
 
     def count_of(c):
         return _F_COUNT, c, None
+
+    def two(fkind, s, c, op2, op3):
+        """The recipes of a 128-bit decimal result's two output rows: the low 64 bits, the signed high word."""
+        return [(fkind, s, c, op2, op3), (fkind | _F_HI, s, c, op2, op3)]
+
+    def numeric(dtype):
+        return dtype in _NUMERIC or is_decimal(dtype)
 
     for ak, func, arg in reqs:
         if func == "count_star":
@@ -378,7 +452,7 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         if func in _PAIRED:
             # (n, Σx, Σy, Cxy) over the rows where both arguments are non-null: count and sums of the pair's masked
             # columns, one Cxy word in an op-4 line; corr adds the masked columns' M2 words (the variance machinery)
-            if any(arg_types[a.key()][0] not in _NUMERIC for a in arg):
+            if not all(numeric(arg_types[a.key()][0]) for a in arg):
                 raise Ineligible(f"{func} type")
             kx, ky = pair_keys(*arg)
             cnt = slot(("count", kx), _MV_COUNT, _MA_ADD_F64)
@@ -403,8 +477,9 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             cif = slot(("cif", ck), _MV_I64, _MA_ADD_U64)
             agg(ak, "cif", cif, None, "long", _F_I64, {"cnt": (_F_I64, cif, None)})
             continue
-        if func in (*_MOMENTS, *_VARIANCE, "sum") and dtype not in _NUMERIC:
+        if func in (*_MOMENTS, *_VARIANCE, "sum") and not numeric(dtype):
             raise Ineligible(f"{func} type")
+        dec = dtype if is_decimal(dtype) else None
         cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
         if func == "count":
             agg(ak, "count", cnt, None, None, _F_COUNT, {"cnt": count_of(cnt)})
@@ -436,6 +511,29 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             val = slot((func[1:], ck), _MV_I64 | (_MV_NOT if func == "bmin" else 0), _MA_MAX)
             fkind = _F_I64 | (_F_NOT if func == "bmin" else 0)
             agg(ak, "i64", val, cnt, "boolean", fkind, {"v": (fkind, val, cnt)})
+        elif dec is not None and func in ("avg", "sum"):
+            # exact: three limb sums in u64 add words that agg_multi leaves at 0 (value kind -1) and win_dec_kernel
+            # fills; SUM and AVG of one argument share them; the partial state of both is the sum, of SUM's type
+            if dec.precision > SUM_PRECISION:
+                raise Ineligible("decimal precision")
+            w = [slot((f"dw{q}", ck), -1, _MA_ADD_U64) for q in range(3)]
+            dec_jobs[("sum", ck)] = (ck, _DEC_SUM, *w)
+            total = two(_F_DEC_SUM, w[0], cnt, w[1], w[2])
+            if func == "sum":
+                agg(ak, "dsum", w[0], cnt, Dec.result_sum(dec), total, {"v": total, "cnt": count_of(cnt)})
+            else:
+                agg(ak, "davg", w[0], cnt, Dec.result_avg(dec), two(_F_DEC_AVG, w[0], cnt, w[1], w[2]),
+                    {f"davg_{dec.precision}_{dec.scale}": total, "cnt": count_of(cnt)})
+        elif dec is not None and not dec.narrow:
+            # MIN / MAX of a two-lane decimal: the hi lane in an ordinary MAX slot, the lo lane's order key in a
+            # slot of an MA_LOKEY line that agg_multi leaves at INT64_MIN and win_dec_kernel fills
+            inv = func == "min"
+            hi = slot((func, ck), _MV_I64 | (_MV_NOT if inv else 0), _MA_MAX)
+            lo = slot(("lo" + func, ck), -1, _MA_LOKEY)
+            lo_of[lo] = hi
+            dec_jobs[(func, ck)] = (ck, _DEC_KEY_MIN if inv else _DEC_KEY_MAX, lo, hi, None)
+            both = two(_F_DEC_MM | (_F_NOT if inv else 0), hi, cnt, lo, None)
+            agg(ak, "dmm", hi, cnt, dec, both, {"v": both, "cnt": count_of(cnt)})
         elif func == "avg":
             sm = slot(("sumf", ck), _MV_F64, _MA_ADD_F64)
             agg(ak, "avg", sm, cnt, "double", _F_AVG, {"s": (_F_F64, sm, cnt), "cnt": count_of(cnt)})
@@ -450,13 +548,15 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             agg(ak, "f64" if is_f else "i64", val, cnt, dtype, fkind, {"v": (fkind, val, cnt), "cnt": count_of(cnt)},
                 f64=is_f)
     order, line_ops = [], []
-    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM):
+    if len(dec_jobs) > MAX_DECIMAL:
+        raise Ineligible("too many decimal arguments")
+    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM, _MA_LOKEY):
         mine = [i for i, sl in enumerate(slots) if sl[2] == op]
         for k in range(0, len(mine), 8):
             chunk = mine[k:k + 8]
             line_ops.append(op)
             order.extend(chunk + [None] * (8 - len(chunk)))
-    if len(order) > 64 or len(plan) > 64:
+    if len(order) > 64 or len(fins) > 64:
         raise Ineligible("too many aggregates")
     where = {i: pos for pos, i in enumerate(order) if i is not None}
     nslots = len(order)
@@ -467,7 +567,8 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         return (kind, *(-1 if s is None else where[s] for s in ss))
 
     fin = [words(*f) for f in fins]
-    pfin = {ak: {suffix: words(*f) for suffix, f in states.items()} for ak, states in pfins.items()}
+    pfin = {ak: {suffix: [words(*h) for h in f] if isinstance(f, list) else words(*f) for suffix, f in states.items()}
+            for ak, states in pfins.items()}
     stride = 8 * len(line_ops)
     # per M2 word: its argument's count word | sum word << 16 (win_combine_kernel); the same three words per
     # variance argument for win_m2_kernel
@@ -479,7 +580,16 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     dcount_word = {key[1]: where[i] for i, (key, _k, _o) in enumerate(slots) if key[0] == "dcount"}
     out = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
                count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word,
-               as_f64=as_f64)
+               as_f64=as_f64, rows=rows)
+    if dec_jobs:
+        # per decimal job the words of win_dec_kernel; per low key word its high word (win_combine_kernel)
+        out["decargs"] = [(ck, kind, where[w0], where[w1], -1 if w2 is None else where[w2])
+                          for ck, kind, w0, w1, w2 in dec_jobs.values()]
+    if lo_of:
+        lodesc = [0] * stride
+        for lo, hi in lo_of.items():
+            lodesc[where[lo]] = where[hi] | 1 << 16
+        out["lodesc"] = lodesc
     if mom_of:
         # per op-4 word: kind << 24 | the words it reads, 6 bits each (win_combine_kernel); per argument or pair the
         # words of its job in the pane's moment pass (win_mom_kernel)
@@ -624,6 +734,7 @@ class DenseWindow:
         self.layout = None              # built from the first pane's evaluated argument types
         self.m2desc_t = self.m2desc_dev = None  # with variance arguments: win_combine_kernel's M2 descriptor
         self.momdesc_t = self.momdesc_dev = None        # with op-4 lines: its M3 / M4 / Cxy descriptor
+        self.lodesc_t = self.lodesc_dev = None          # with low-key lines (two-lane decimal MIN / MAX): the high words
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
         self.free = list(range(ring_slots))    # free pane slots (a heap: the lowest is taken first)
         self.disabled = False
@@ -706,11 +817,16 @@ class DenseWindow:
         self.layout = L
         # agg_multi (host ``line_ops_t``) sees an M2 line as an f64 add line of unused slots, so every pane starts
         # its M2 words at 0.0; the ring kernels (``line_ops_dev``) see MA_M2
-        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op in (_MA_M2, _MA_MOM) else op for op in L["line_ops"]],
-                                       dtype=torch.int32)
+        # and a low-key line as a max line of unused slots, so every pane starts its low key words at INT64_MIN
+        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op in (_MA_M2, _MA_MOM) else _MA_MAX if op == _MA_LOKEY else op
+                                        for op in L["line_ops"]], dtype=torch.int32)
         self.line_ops_dev = torch.tensor(L["line_ops"], dtype=torch.int32).to(self.device)
         self.m2desc_t = self.m2desc_dev = None
         self.momdesc_t = self.momdesc_dev = None
+        self.lodesc_t = self.lodesc_dev = None
+        if "lodesc" in L:
+            self.lodesc_t = torch.tensor(L["lodesc"], dtype=torch.int32)
+            self.lodesc_dev = self.lodesc_t.to(self.device)
         if L["m2args"] or "momdesc" in L:
             self.m2desc_t = torch.tensor(L["m2desc"], dtype=torch.int32)
             self.m2desc_dev = self.m2desc_t.to(self.device)
@@ -852,7 +968,9 @@ class DenseWindow:
                 c = evaluate(a, scope, ctx)
                 if isinstance(c, ConstColumn):
                     c = c.materialize()
-                if not isinstance(c, PrimColumn) or is_decimal(c.dtype) or c.data.dim() != 1:
+                # a decimal argument keeps its storage: one int64 lane per row, or two for more than 18 digits
+                if not isinstance(c, PrimColumn) or \
+                        c.data.dim() != (2 if is_decimal(c.dtype) and not c.dtype.narrow else 1):
                     raise Ineligible("argument type")
                 args[a.key()] = c
             if isinstance(arg, tuple) and pair_keys(*arg)[0] not in args:
@@ -862,9 +980,13 @@ class DenseWindow:
                     x.valid.to(torch.bool) & y.valid.to(torch.bool)
                 kx, ky = pair_keys(*arg)
                 args[kx], args[ky] = PrimColumn(x.dtype, x.data, both), PrimColumn(y.dtype, y.data, both)
+        dec_types = {k: str(c.dtype) for k, c in args.items() if is_decimal(c.dtype)}
         if self.layout is None:
             self._build_layout(keys, args, dargs)
+            self.dec_types = dec_types
         else:
+            if dec_types != self.dec_types:        # the layout's words and win_dec_kernel's lanes follow the types
+                raise Ineligible("argument types changed")
             for (dt, kind, *_), k in zip(self.keys, keys):
                 if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
                     raise Ineligible("key types changed")
@@ -912,7 +1034,10 @@ class DenseWindow:
                 continue
             d = c.data
             if key[0] == "sumf" or (kind & 3) in (_MV_F64, _MV_F64_ORD):
-                d = d.to(torch.float64)
+                # (a decimal in the f64 families: the double Spark's cast gives)
+                d = Dec.to_double(c).data if is_decimal(c.dtype) else d.to(torch.float64)
+            elif d.dim() == 2:                     # MIN / MAX of a two-lane decimal: the high key is the hi lane
+                d = d[:, 1]
             elif d.dtype != torch.int64:
                 d = d.to(torch.int64)
             d = d.contiguous()
@@ -940,14 +1065,29 @@ class DenseWindow:
                 m.a[k] = _MomArg(d.data_ptr(), 0 if ky is None else xs[ky][0].data_ptr(),
                                  0 if v is None else v.data_ptr(), cw, sw, syw, w0, w1, 0)
             N.call("dxa_win_mom", self._second_pass(m, len(L["momargs"]), gid, ring_ptr, n), st)
+        if L.get("decargs") and n > 0:
+            # the decimal pass: limb sums and low key words straight from the decimal columns' storage (win_dec_kernel
+            # reads them in place with a lane stride of 1 or 2), all of the statement's jobs in one launch
+            m = _DecArgs()
+            for k, (ck, kind, w0, w1, w2) in enumerate(L["decargs"]):
+                c = args[ck]
+                d = c.data.contiguous()
+                v = N.u8(c.valid)
+                if v is not None:
+                    v = v.contiguous()
+                hold += [d, v]
+                m.a[k] = _DecJob(d.data_ptr(), 0 if v is None else v.data_ptr(), d.dim(), kind, w0, w1, w2, 0)
+            N.call("dxa_win_dec", self._second_pass(m, len(L["decargs"]), gid, ring_ptr, n), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
 
     def _descs(self):
         """The combine's descriptors for ``dxa_win_answer`` / ``dxa_win_combine_block``: ``m2desc`` on the device and
-        on the host, ``momdesc`` likewise; 0 where the layout has none, which picks the combine without that branch."""
-        return N.ptr(self.m2desc_dev), N.ptr(self.m2desc_t), N.ptr(self.momdesc_dev), N.ptr(self.momdesc_t)
+        on the host, ``momdesc`` and ``lodesc`` likewise; 0 where the layout has none, which picks the combine without
+        that branch."""
+        return (N.ptr(self.m2desc_dev), N.ptr(self.m2desc_t), N.ptr(self.momdesc_dev), N.ptr(self.momdesc_t),
+                N.ptr(self.lodesc_dev), N.ptr(self.lodesc_t))
 
     def _second_pass(self, m, nargs: int, gid: torch.Tensor, ring_ptr: int, n: int) -> int:
         """The fields ``_M2Args`` and ``_MomArgs`` share, after their jobs: the pane's group ids and ring slot → the
@@ -1046,7 +1186,7 @@ class DenseWindow:
         if self.global_form and nout == 0:
             # no row passed the WHERE anywhere in the window: Spark's one row — counts 0, everything else NULL
             return [], self._finals([(torch.zeros(1, dtype=torch.int64, device=self.device),
-                                      torch.zeros(1, dtype=torch.bool, device=self.device)) for _ in L["plan"]]), 1
+                                      torch.zeros(1, dtype=torch.bool, device=self.device)) for _ in L["fin"]]), 1
         out_keys = []
         for j, (dt, kind, vals, lens, valid) in enumerate(self.keys):
             v = ovalid[j, :nout].view(torch.bool)
@@ -1067,13 +1207,17 @@ class DenseWindow:
         return ([] if self.global_form else out_keys), self._finals(cols), nout
 
     def _finals(self, cols) -> Dict:
-        """{agg key → column} from the emitted (int64 words, validity) per ``plan`` entry: a count (no count slot)
+        """{agg key → column} from the emitted (int64 words, validity) per ``fin`` row: a count (no count slot)
         is a never-NULL long, everything else has the planned dtype ``dt`` over doubles (``as_f64``), booleans or the
-        words as they are."""
+        words as they are.  A ``plan`` entry with two rows is a 128-bit decimal (lo, hi), packed as ``dt`` stores it:
+        lo alone for up to 18 digits, else [n, 2]."""
         L = self.layout
         finals = {}
-        for (ak, _kind, _s, c, dt), f64, (v, ok) in zip(L["plan"], L["as_f64"], cols):
-            if c is None:
+        for (ak, _kind, _s, c, dt), f64, (r0, nr) in zip(L["plan"], L["as_f64"], L["rows"]):
+            v, ok = cols[r0]
+            if nr == 2:
+                finals[ak] = PrimColumn(dt, Dec.pack(cols[r0 + 1][0], v, dt), ok)
+            elif c is None:
                 finals[ak] = PrimColumn("long", v)
             else:
                 finals[ak] = PrimColumn(dt, v.view(torch.float64) if f64 else v.to(torch.bool) if dt == "boolean"
@@ -1111,7 +1255,7 @@ class DenseWindow:
                 f = L["pfin"].get(ak, {}).get(suffix)
                 if f is None:
                     raise Ineligible(f"partial {suffix}")
-                out.append(f)
+                out.extend(f if isinstance(f, list) else [f])      # (a 128-bit decimal state: two rows)
         return out
 
     def _partials(self, cols, out_keys, nout, proto, pplan, key_names):
@@ -1124,7 +1268,11 @@ class DenseWindow:
                 like = proto.column(nm)
                 v, ok = cols[j]
                 j += 1
-                if suffix == "cnt":
+                if isinstance(self.layout["pfin"][ak][suffix], list):
+                    # a 128-bit decimal state (lo, hi) as the prototype's type stores it
+                    got[nm] = PrimColumn(like.dtype, Dec.pack(cols[j][0], v, like.dtype), ok)
+                    j += 1
+                elif suffix == "cnt":
                     got[nm] = PrimColumn(like.dtype, v)
                 elif isinstance(like, PrimColumn) and like.data.dtype == torch.float64:
                     got[nm] = PrimColumn(like.dtype, v.view(torch.float64), ok)

@@ -28,8 +28,13 @@
 // The variance family (M2) and skewness / kurtosis / corr / covar (M3, M4, Cxy) keep centred sums per pane and group:
 // second passes over the pane fill them (win_m2_kernel, win_mom_kernel) and win_combine merges slots by the multi-way
 // form of Chan's update.
+// Decimal arguments stay exact: SUM / AVG keep three 32-bit limb sums per pane and group as ordinary MA_ADD_U64 words
+// (win_dec_kernel fills them from the decimal column in place, win_emit_kernel reassembles the 128-bit total and, for
+// AVG, divides it exactly with HALF_UP rounding); MIN / MAX of a two-lane decimal keep a two-word order key, the hi
+// word an ordinary MA_MAX word and the lo word in a line of the combine op MA_LOKEY (described by ``lodesc``).
 // Every layout goes through the same two host entry points, dxa_win_answer (steps 3-5) and dxa_win_combine_block; the
-// descriptors a layout passes (none, m2desc, m2desc + momdesc) pick the win_combine_kernel instantiation.
+// descriptors a layout passes (none, m2desc, m2desc + momdesc; with or without lodesc) pick the win_combine_kernel
+// instantiation.
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -50,6 +55,12 @@ enum : int32_t { MA_M2 = 3 };
 // (kind << 24 | four 6-bit word indices).  agg_multi sees such a line as unused f64 words, win_mom_kernel fills it.
 enum : int32_t { MA_MOM = 4 };
 enum : int32_t { MOM_M3 = 1, MOM_M4 = 2, MOM_CXY = 3 };
+// The low word of a two-word order key (MIN / MAX of a decimal held as two int64 lanes): the key's high word is an
+// ordinary MA_MAX word of the same row (the hi lane, complemented for MIN), this word holds the lo lane's unsigned
+// order mapped to signed (lo ^ 2^63, complemented for MIN) of the rows whose high key equals the row's high word.
+// ``lodesc`` names per word its high word (index | 1 << 16; 0: padding).  agg_multi sees such a line as MA_MAX with
+// unused slots (every pane starts it at INT64_MIN), win_dec_kernel fills it after the high word is finished.
+enum : int32_t { MA_LOKEY = 5 };
 
 // same layout as hash_groupby.hip's KeyCols (built by dxa/ops/hashing.py key_cols)
 struct KeyCol {
@@ -110,7 +121,11 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
 //   Cxy = Σ_s [ Cxy_s + n_s δ_s ε_s ]
 // Every right-hand side reads the slots' words only, never a combined word, so each output word is computed on its
 // own like M2.  A padding word of such a line (kind 0) is written as 0.0.  Without kMom the branch is compiled out.
-template <bool kBlock, bool kM2, bool kMom>
+// ``kKey``: the layout has MA_LOKEY lines and ``lodesc`` [stride] names each of their words' high word.  Such a word
+// combines as the max of the slots' words over the slots whose high word equals the max of the high words, so the
+// (high, low) pair is the lexicographic max; slots that are all the identity (INT64_MIN twice) give the identity.
+// Without kKey the branch is compiled out.
+template <bool kBlock, bool kM2, bool kMom, bool kKey>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
                                                           int32_t nslots_in, int32_t stride,
@@ -118,7 +133,8 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
                                                           const int32_t* __restrict__ scal, int32_t gcap,
                                                           int32_t fixed_rows, unsigned long long* __restrict__ out,
                                                           const int32_t* __restrict__ m2desc,
-                                                          const int32_t* __restrict__ momdesc) {
+                                                          const int32_t* __restrict__ momdesc,
+                                                          const int32_t* __restrict__ lodesc) {
   int32_t ng = scal[0];
   if (ng > gcap) ng = gcap;
   const int64_t held = (int64_t)ng * stride;
@@ -189,6 +205,23 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
         }
       }
       out[idx] = (unsigned long long)__double_as_longlong(acc);
+    } else if (kKey && op == MA_LOKEY) {
+      const int32_t dsc = lodesc[w];
+      const int64_t hi_at = idx - w + (dsc & 0xffff);
+      const int ns_in = dsc ? nslots : 0;
+      long long top = (long long)0x8000000000000000ull;
+      for (int s = 0; s < ns_in; ++s) {
+        const long long h = (long long)ring[(int64_t)slots[s] * slot_words + hi_at];
+        top = h > top ? h : top;
+      }
+      long long acc = (long long)0x8000000000000000ull;
+      for (int s = 0; s < ns_in; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        if ((long long)ring[base + hi_at] != top) continue;
+        const long long v = (long long)ring[base + idx];
+        acc = v > acc ? v : acc;
+      }
+      out[idx] = (unsigned long long)acc;
     } else {
       long long acc = (long long)0x8000000000000000ull;
       for (int s = 0; s < nslots; ++s) {
@@ -375,6 +408,94 @@ __global__ __launch_bounds__(256) void win_mom_kernel(const MomArgs m) {
   }
 }
 
+// 2d. the same second pass for decimal arguments, read in place: ``x`` is the column's int64 storage, one lane per
+// row (a value below 10^18, hi = its sign) or two (lo at 2i, hi at 2i + 1).
+//   DEC_SUM: the row adds lo & 0xffffffff, lo >> 32 (unsigned) and hi (signed) into three MA_ADD_U64 words of its
+//            group.  Each word is exact while a group has fewer than 2^31 rows in the window, the words combine with
+//            the ordinary u64 add, and integer adds make the result independent of the arrival order.
+//   DEC_KEY_MAX / DEC_KEY_MIN: agg_multi has finished the group's high key word (w1); a row whose high key (hi, ~hi
+//            for MIN) equals it puts its low key (lo ^ 2^63, complemented for MIN) into the MA_LOKEY word w0 by max.
+// Ids below kM2LdsGroups go through LDS u64 arrays and are flushed with one global atomic per touched group, word
+// and workgroup; the others go straight to the row with non-returning 64-bit atomics.  Rows of the dump row and
+// rows with a NULL argument are skipped.  One launch covers all decimal jobs of a statement.
+constexpr int kMaxDecJobs = 8;
+enum : int32_t { DEC_SUM = 0, DEC_KEY_MAX = 1, DEC_KEY_MIN = 2 };
+struct DecJob {
+  const long long* x;
+  const uint8_t* valid;
+  int32_t lanes;           // 1 or 2
+  int32_t kind;
+  int32_t w0;              // words of the slot row: DEC_SUM: the three limb sums; keys: the low word, the high word
+  int32_t w1;
+  int32_t w2;
+  int32_t pad;
+};
+struct DecArgs {
+  DecJob a[kMaxDecJobs];
+  const int32_t* gid;
+  unsigned long long* row; // the ring slot: [gcap + 1][stride]
+  int64_t n;
+  int32_t gcap;
+  int32_t stride;
+  int32_t nargs;
+  int32_t pad;
+};
+
+__global__ __launch_bounds__(256) void win_dec_kernel(const DecArgs m) {
+  __shared__ unsigned long long part[3][kM2LdsGroups];
+  constexpr unsigned long long kLowest = 0x8000000000000000ull;
+  const int32_t lds_groups = m.gcap < kM2LdsGroups ? m.gcap : kM2LdsGroups;
+  for (int k = 0; k < m.nargs; ++k) {
+    const DecJob a = m.a[k];
+    const bool sum = a.kind == DEC_SUM;
+    for (int g = threadIdx.x; g < kM2LdsGroups; g += blockDim.x) {
+      part[0][g] = sum ? 0ull : kLowest;
+      part[1][g] = 0ull;
+      part[2][g] = 0ull;
+    }
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m.n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int32_t g = m.gid[i];
+      if (g < 0 || g >= m.gcap || (a.valid && !a.valid[i])) continue;
+      const long long lo = a.x[i * a.lanes];
+      const long long hi = a.lanes == 2 ? a.x[i * 2 + 1] : (lo >> 63);
+      unsigned long long* r = m.row + (int64_t)g * m.stride;
+      if (sum) {
+        const unsigned long long l0 = (unsigned long long)lo & 0xffffffffull, l1 = (unsigned long long)lo >> 32;
+        if (g < kM2LdsGroups) {
+          atomicAdd(&part[0][g], l0);
+          atomicAdd(&part[1][g], l1);
+          if (hi) atomicAdd(&part[2][g], (unsigned long long)hi);
+        } else {
+          atomicAdd(r + a.w0, l0);
+          atomicAdd(r + a.w1, l1);
+          if (hi) atomicAdd(r + a.w2, (unsigned long long)hi);
+        }
+      } else {
+        const bool mn = a.kind == DEC_KEY_MIN;
+        if ((mn ? ~hi : hi) != (long long)r[a.w1]) continue;
+        long long key = lo ^ (long long)kLowest;
+        if (mn) key = ~key;
+        if (g < kM2LdsGroups) atomicMax((long long*)&part[0][g], key);
+        else atomicMax((long long*)(r + a.w0), key);
+      }
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < lds_groups; g += blockDim.x) {
+      unsigned long long* r = m.row + (int64_t)g * m.stride;
+      if (sum) {
+        const unsigned long long v0 = part[0][g], v1 = part[1][g], v2 = part[2][g];
+        if (v0) atomicAdd(r + a.w0, v0);
+        if (v1) atomicAdd(r + a.w1, v1);
+        if (v2) atomicAdd(r + a.w2, v2);
+      } else if (part[0][g] != kLowest) {
+        atomicMax((long long*)(r + a.w0), (long long)part[0][g]);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 __device__ __forceinline__ uint64_t row_hash(const KeyCols& a, int64_t i) {
   uint64_t h = 0;
   for (int j = 0; j < a.ncols; ++j) {
@@ -509,6 +630,12 @@ enum : int { F_COUNT = 0, F_I64 = 1, F_F64 = 2, F_AVG = 3, F_F64_ORD = 4, F_VAR_
 //   F_SKEW       sqrt(n) · M3 / M2^1.5, op2 = M2;  F_KURT  n · M4 / M2² − 3, op2 = M2; NaN unless M2 > 0
 // (Spark 2.4's Covariance / Corr / CentralMomentAgg; n = 0 is NULL by the validity rule, as everywhere).
 enum : int { F_COVAR_POP = 32, F_COVAR_SAMP = 64, F_CORR = 96, F_SKEW = 128, F_KURT = 160, F_KIND_MASK = 7 | 224 };
+// Decimal results are 128-bit integers and take two output rows each, the same recipe once without and once with
+// F_HI (the bit F_SQRT has in the variance kinds): the low 64 bits, then the signed high word.
+//   F_DEC_SUM  pos, op2, op3 = the limb sums Σ (lo & 0xffffffff), Σ (lo >> 32), Σ hi: their carry-propagated total
+//   F_DEC_AVG  the same words, cnt = n: total · 10^4 / n rounded HALF_UP (away from zero at a tie), exactly
+//   F_DEC_MM   pos = the high key word (F_NOT: MIN, complemented), op2 = the low key word: the key mapping undone
+enum : int { F_DEC_MM = 7, F_DEC_SUM = 192, F_DEC_AVG = 224, F_HI = 16 };
 struct EmitArgs {
   const long long* acc;
   int32_t stride;
@@ -527,6 +654,49 @@ struct EmitArgs {
   const int32_t* scal;
   int32_t gcap;
 };
+
+// the 128-bit total w0 + w1 · 2^32 + w2 · 2^64 (mod 2^128) of a decimal argument's limb sums
+__device__ __forceinline__ void dec_total(unsigned long long w0, unsigned long long w1, unsigned long long w2,
+                                          unsigned long long& lo, long long& hi) {
+  lo = w0 + (w1 << 32);
+  hi = (long long)(w2 + (w1 >> 32) + (lo < w0 ? 1ull : 0ull));
+}
+
+// (hi, lo) · 10^4 / n rounded HALF_UP on the magnitude, for 0 < n < 2^31: q, r = |v| divmod n by schoolbook division
+// over 32-bit limbs (the running remainder is below n, so every step fits 64 bits), then
+// q · 10^4 + ⌊(2 · r · 10^4 + n) / 2n⌋ — the second term is the rounded quotient of the remainder, at most 10^4 —
+// and the sign goes back on.  No 128-bit division: only 64-bit ones, which the compiler expands inline.
+__device__ __forceinline__ void dec_avg(unsigned long long& lo, long long& hi, unsigned long long n) {
+  const bool neg = hi < 0;
+  unsigned long long ml = lo, mh = (unsigned long long)hi;
+  if (neg) {
+    ml = 0ull - lo;
+    mh = ~mh + (lo == 0ull ? 1ull : 0ull);
+  }
+  const unsigned long long x[4] = {ml & 0xffffffffull, ml >> 32, mh & 0xffffffffull, mh >> 32};
+  unsigned long long q[4], rem = 0;
+#pragma unroll
+  for (int i = 3; i >= 0; --i) {
+    const unsigned long long cur = (rem << 32) | x[i];
+    q[i] = cur / n;
+    rem = cur - q[i] * n;
+  }
+  unsigned long long carry = (2ull * rem * 10000ull + n) / (2ull * n);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned long long t = q[i] * 10000ull + carry;      // q[i] < 2^32: below 2^46
+    q[i] = t & 0xffffffffull;
+    carry = t >> 32;
+  }
+  ml = q[0] | (q[1] << 32);
+  mh = q[2] | (q[3] << 32);
+  if (neg) {
+    mh = ~mh + (ml == 0ull ? 1ull : 0ull);
+    ml = 0ull - ml;
+  }
+  lo = ml;
+  hi = (long long)mh;
+}
 
 __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCols d) {
   const int32_t kept = e.scal[2];
@@ -588,6 +758,23 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
           o = m2 > 0.0 ? __double_as_longlong(c * __longlong_as_double(v) / (m2 * m2) - 3.0) : 0x7ff8000000000000ll;
           break;
         }
+        case F_DEC_SUM:
+        case F_DEC_AVG: {
+          unsigned long long lo;
+          long long hi;
+          dec_total((unsigned long long)row[e.pos[r]], (unsigned long long)row[e.op2[r]],
+                    (unsigned long long)row[e.op3[r]], lo, hi);
+          if ((k & F_KIND_MASK) == F_DEC_AVG) dec_avg(lo, hi, c > 1.0 ? (unsigned long long)c : 1ull);
+          o = (k & F_HI) ? hi : (long long)lo;
+          break;
+        }
+        case F_DEC_MM: {
+          // v is the high word with MIN's complement undone; the low key: the complement, then the order mapping
+          long long l = row[e.op2[r]];
+          if (k & F_NOT) l = ~l;
+          o = (k & F_HI) ? v : (l ^ (long long)0x8000000000000000ull);
+          break;
+        }
         default: o = v; break;
       }
       e.dst[(int64_t)r * e.gcap + p] = o;
@@ -632,7 +819,8 @@ __global__ __launch_bounds__(256) void win_remap_slot_kernel(const unsigned long
        idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = idx / stride;
     const int w = (int)(idx - p * stride);
-    unsigned long long v = line_op[w >> 3] == MA_MAX_I64 ? 0x8000000000000000ull : 0ull;
+    const int op = line_op[w >> 3];
+    unsigned long long v = (op == MA_MAX_I64 || op == MA_LOKEY) ? 0x8000000000000000ull : 0ull;
     if (p < live) v = src[out_idx[p] * stride + w];
     dst[idx] = v;
   }
@@ -808,7 +996,8 @@ DXA_API int dxa_win_init(uint64_t* keys, int32_t* gid_of_slot, int64_t cap, void
 // ---- the combine and the window's answer: one entry point each, for every layout ---------------------------------
 // A layout with MA_M2 lines passes ``m2desc`` [stride] on the device (win_combine_kernel) and ``m2desc_host``, the same
 // words for the bounds check here; one with MA_MOM lines also ``momdesc`` / ``momdesc_host``, and then ``m2desc`` is
-// required too (all zero without M2 lines).  A layout without such lines passes null for both pairs.
+// required too (all zero without M2 lines).  A layout without such lines passes null for both pairs.  A layout with
+// MA_LOKEY lines passes ``lodesc`` / ``lodesc_host`` the same way, independently of the other two.
 
 static bool m2desc_ok(const int32_t* host_desc, int32_t stride) {
   for (int w = 0; w < stride; ++w) {
@@ -831,10 +1020,21 @@ static bool momdesc_ok(const int32_t* host_desc, int32_t stride) {
   return true;
 }
 
+static bool lodesc_ok(const int32_t* host_desc, int32_t stride) {
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d && ((d >> 16) != 1 || (d & 0xffff) >= stride)) return false;
+  }
+  return true;
+}
+
 static bool descs_ok(const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
-                     const int32_t* momdesc_host, int32_t stride) {
-  if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc)) return false;
-  return (!m2desc || m2desc_ok(m2desc_host, stride)) && (!momdesc || momdesc_ok(momdesc_host, stride));
+                     const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
+                     int32_t stride) {
+  if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc) || !lodesc != !lodesc_host)
+    return false;
+  return (!m2desc || m2desc_ok(m2desc_host, stride)) && (!momdesc || momdesc_ok(momdesc_host, stride)) &&
+         (!lodesc || lodesc_ok(lodesc_host, stride));
 }
 
 static bool folds_ok(const PairFolds* pf, int32_t stride) {
@@ -847,12 +1047,13 @@ static bool folds_ok(const PairFolds* pf, int32_t stride) {
   return true;
 }
 
-// the further operand words of the kinds above F_SQRT (no other kind reads op2 / op3)
+// the further operand words of the kinds above F_SQRT and of F_DEC_MM (no other kind reads op2 / op3)
 static bool emit_ok(const EmitArgs& ea, int32_t stride) {
   for (int r = 0; r < ea.nreq && r < kMaxEmit; ++r) {
     const int k = ea.kind[r] & F_KIND_MASK;
     if (k >= F_CORR && (ea.op2[r] < 0 || ea.op2[r] >= stride)) return false;
-    if (k == F_CORR && (ea.op3[r] < 0 || ea.op3[r] >= stride)) return false;
+    if ((k == F_CORR || k >= F_DEC_SUM) && (ea.op3[r] < 0 || ea.op3[r] >= stride)) return false;
+    if (k == F_DEC_MM && (ea.op2[r] < 0 || ea.op2[r] >= stride)) return false;
   }
   return true;
 }
@@ -862,14 +1063,17 @@ static bool emit_ok(const EmitArgs& ea, int32_t stride) {
 template <bool kBlock>
 static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t stride, const int32_t* slots,
                            int32_t nslots, const int32_t* line_op, const int32_t* scal, unsigned long long* out,
-                           const int32_t* m2desc, const int32_t* momdesc, hipStream_t s) {
+                           const int32_t* m2desc, const int32_t* momdesc, const int32_t* lodesc, hipStream_t s) {
   const int32_t rows = kBlock ? gcap + 1 : gcap;
-  auto kernel = momdesc  ? win_combine_kernel<kBlock, true, true>
-                : m2desc ? win_combine_kernel<kBlock, true, false>
-                         : win_combine_kernel<kBlock, false, false>;
-  hipLaunchKernelGGL(kernel, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s, ring,
-                     (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap, kBlock ? rows : 0, out,
-                     m2desc, momdesc);
+  auto plain = momdesc  ? win_combine_kernel<kBlock, true, true, false>
+               : m2desc ? win_combine_kernel<kBlock, true, false, false>
+                        : win_combine_kernel<kBlock, false, false, false>;
+  auto keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true>
+               : m2desc ? win_combine_kernel<kBlock, true, false, true>
+                        : win_combine_kernel<kBlock, false, false, true>;
+  hipLaunchKernelGGL(lodesc ? keyed : plain, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s,
+                     ring, (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap,
+                     kBlock ? rows : 0, out, m2desc, momdesc, lodesc);
 }
 
 // a block of ring slots pre-combined into another ring slot (every row is written, so groups the dictionary gains
@@ -877,11 +1081,12 @@ static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t
 DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
                                   const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
                                   const int32_t* m2desc_host, const int32_t* momdesc, const int32_t* momdesc_host,
-                                  void* st) {
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, stride)) return (int)hipErrorInvalidValue;
+                                  const int32_t* lodesc, const int32_t* lodesc_host, void* st) {
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, stride))
+    return (int)hipErrorInvalidValue;
   unsigned long long* r = (unsigned long long*)ring;
   launch_combine<true>(r, gcap, stride, slots, nslots, line_op, scal, r + (int64_t)dst * (gcap + 1) * stride, m2desc,
-                       momdesc, (hipStream_t)st);
+                       momdesc, lodesc, (hipStream_t)st);
   return (int)hipGetLastError();
 }
 
@@ -893,16 +1098,17 @@ DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const
                            const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
                            int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
                            const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
-                           const int32_t* momdesc_host, void* st) {
+                           const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
+                           void* st) {
   hipStream_t s = (hipStream_t)st;
   const EmitArgs* ea = (const EmitArgs*)emit;
   const PairFolds* pf = (const PairFolds*)folds;
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, stride) || !folds_ok(pf, stride) ||
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, stride) || !folds_ok(pf, stride) ||
       (ea && (!dictcols || !emit_ok(*ea, stride))))
     return (int)hipErrorInvalidValue;
   hipMemsetAsync(scal + 2, 0, 4, s);
   launch_combine<false>((const unsigned long long*)ring, gcap, stride, slots, nslots, line_op, scal,
-                        (unsigned long long*)acc, m2desc, momdesc, s);
+                        (unsigned long long*)acc, m2desc, momdesc, lodesc, s);
   for (int k = 0; pf && k < pf->n; ++k)
     hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf->p[k].pcap + 15) >> 4, 256, 256 * 8)),
                        dim3(256), 0, s, pf->p[k], slots, nslots, scal, gcap, (double*)acc, stride);
@@ -925,7 +1131,7 @@ DXA_API int dxa_win_live(const void* ring, int32_t gcap, int32_t stride, const i
                          const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
                          int64_t* out_idx, void* st) {
   return dxa_win_answer(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 // The dictionary's key columns into fresh ones (``dst`` is zero-filled; earlier batches' output strings are views of
@@ -1063,5 +1269,25 @@ DXA_API int dxa_win_mom(const void* args, void* st) {
   }
   if (m.n <= 0 || m.nargs == 0) return 0;
   hipLaunchKernelGGL(win_mom_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
+  return (int)hipGetLastError();
+}
+
+// ---- decimal SUM / AVG / two-lane MIN / MAX: the pane's decimal pass -------------------------------------------------
+
+DXA_API int dxa_win_dec_size() { return (int)sizeof(DecArgs); }
+
+// a pane's limb sums and low key words, on the same stream after dxa_aggregate_multi filled the slot (win_dec_kernel)
+DXA_API int dxa_win_dec(const void* args, void* st) {
+  const DecArgs& m = *(const DecArgs*)args;
+  if (m.nargs < 0 || m.nargs > kMaxDecJobs || m.gcap < 0 || m.stride <= 0) return (int)hipErrorInvalidValue;
+  for (int k = 0; k < m.nargs; ++k) {
+    const DecJob& a = m.a[k];
+    if (!a.x || (a.lanes != 1 && a.lanes != 2) || a.kind < DEC_SUM || a.kind > DEC_KEY_MIN || a.w0 < 0 ||
+        a.w0 >= m.stride || a.w1 < 0 || a.w1 >= m.stride)
+      return (int)hipErrorInvalidValue;
+    if (a.kind == DEC_SUM ? (a.w2 < 0 || a.w2 >= m.stride) : a.lanes != 2) return (int)hipErrorInvalidValue;
+  }
+  if (m.n <= 0 || m.nargs == 0) return 0;
+  hipLaunchKernelGGL(win_dec_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
   return (int)hipGetLastError();
 }

@@ -328,6 +328,11 @@ _F_VAR_SAMP, _F_VAR_POP, _F_SQRT = 5, 6, 16
 _MA_MOM = 4
 _MOM_M3, _MOM_M4, _MOM_CXY = 1, 2, 3
 _F_COVAR_POP, _F_COVAR_SAMP, _F_CORR, _F_SKEW, _F_KURT = 32, 64, 96, 128, 160
+# and for exact decimals: the combine op of the low word of a two-word MIN / MAX key (its high word is an _MA_MAX
+# word), and the finishing kinds of the 128-bit results — two output rows each, the second with _F_HI
+_MA_LOKEY = 5
+_F_DEC_MM, _F_DEC_SUM, _F_DEC_AVG, _F_HI = 7, 192, 224, 16
+_DEC_SUM, _DEC_KEY_MAX, _DEC_KEY_MIN = 0, 1, 2           # win_dec_kernel's job kinds
 _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096
