@@ -953,8 +953,11 @@ def _paned_aggregate(sel: A.Select, t, alias: str, ctx) -> Optional[Table]:
         ok = bool(aggs or sel.group_by) and not any(W.window_calls(e) for e, _ in items)
         # COUNT(DISTINCT x) has no mergeable partial, but the dense ring answers it (window_dense.py): a statement
         # whose aggregates are decomposable apart from one-argument distinct counts is tried there and nowhere else
-        dcounts = {k: c for k, c in aggs.items() if c.distinct and c.name == "count" and len(c.args) == 1 and
-                   not c.star and c.name not in ctx.udafs}
+        # — and so are max_by / min_by, whose state (a row pick) the ring keeps per pane and group: the aggregates
+        # only the ring can answer
+        dcounts = {k: c for k, c in aggs.items() if c.name not in ctx.udafs and (
+            (c.distinct and c.name == "count" and len(c.args) == 1 and not c.star) or
+            (c.name in ("max_by", "min_by") and not c.distinct and len(c.args) == 2))}
         dense_only = bool(dcounts)
         ok = ok and D.decomposable({k: c for k, c in aggs.items() if k not in dcounts}, ctx)
         exprs = [e for e, _ in items] + list(sel.group_by) + ([sel.where] if sel.where is not None else []) + (

@@ -17,7 +17,8 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
 
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over numeric (decimals
 included, below), boolean or timestamp arguments (and COUNT(DISTINCT x), the variance family and corr / covar_pop /
-covar_samp / skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some), with plain key columns,
+covar_samp / skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some; first / last / max_by /
+min_by, below), with plain key columns,
 deterministic, on a GPU.  With N ranks each rank's window
 comes out of its ring as a partial table of ``distagg.local_partials``' layout and goes through the same key
 exchange and merge as the paned path (``dense_partials``).  Anything else — and any batch whose dictionary
@@ -110,14 +111,49 @@ argument's — and the partial states are ``distagg._partials``': SUM ("v" of th
 ("davg_{p}_{s}" — the sum —, "cnt"), MIN / MAX ("v", "cnt").  Decimal group keys and COUNT(DISTINCT decimal)
 remain ineligible ("key type", "argument type").
 
+**Row picks: first / last / max_by / min_by** (``_PICKS``; ``first_value`` / ``last_value`` are first / last; up to
+``MAX_PICK`` different rank jobs and as many payload jobs per statement, fallback reason "too many pick arguments").
+All four are one state per pane and group: which row wins, and that row's value.  The window's row order is that of
+the materialised view: the panes in the order of ``PanedTable.pieces()`` — the view's pane list, never the order of
+the pane keys —, a pane's rows in table order, a clipped pane's in-range rows in table order.  ``first(x)`` /
+``last(x)`` give x of the group's first / last row that passes WHERE, NULL if that x is NULL (NULLs are not skipped);
+``max_by(x, y)`` / ``min_by(x, y)`` x of the row with the largest / smallest non-NULL y, the first such row among
+equals, NULL without one or if that x is NULL.  The words: a rank word R in a line of the combine op ``MA_PICK_RANK``
+(identity INT64_MIN; INT64_MAX − row index where the smallest index wins, the row index for ``last``), and per payload
+argument a word P (the 64 bits of x) and a word V (1.0 / 0.0: x non-NULL / NULL) in lines of ``MA_PICK_VAL`` (identity
+0); agg_multi sees both kinds of line as unused.  max_by / min_by also have a key word K, the ordinary ``MA_MAX`` slot
+of y (``MV_NOT`` for min_by) that MAX(y) / MIN(y) of the same statement share.  first(a) and first(b) share R,
+max_by(a, y) and max_by(b, y) share K and R; each payload argument has its own P and V.  After the multi-aggregate
+``dxa_win_pick`` issues two launches per accumulated pane: ``win_pick_kernel`` puts the rank of every row that counts —
+for a keyed job: y non-NULL and its key equal to the slot's finished K — into R by a 64-bit max (ids below the LDS
+bound through an LDS array), then ``win_pick_gather_kernel`` decodes R per group in use (the device's counter, no host
+read), checks the index against the pane's rows and copies x's bits and validity.  ``pickdesc`` names per word of the
+two ops its R word, its K word and the direction; the combine (one more ``win_combine_kernel`` flag, instantiated only
+with a ``pickdesc``) takes such a word from one slot: among the slots — in the order of the ``slots`` array — whose
+R is not the identity and, for a keyed pick, whose K is the max K, the first, or the last for ``last``.  So for a
+layout with picks ``_enqueue`` passes the slots in the window's row order (``_ordered_slots``): scratch slots at their
+panes' places, a complete block as its pre-combined slot only where its members stand together (combined in that
+order).  Layouts without picks keep their slot order, so their f64 sums add in the order they always did.
+``win_emit_kernel`` needs no new kind: P is finished by the default kind with V as its count word, and "count > 0 →
+valid" makes a NULL x or a group without a row NULL.  The result has x's type: boolean is read back as ``!= 0``, float
+and double from the stored double's bits, a narrow decimal keeps its ``DecimalType``.  Eligible x and y fit one 64-bit
+word: byte … long, boolean, timestamp / date, float / double, decimal(p ≤ 18); anything else is "argument type".  A
+double y orders as ``query._arg_extreme`` orders it — NaN the largest, -0.0 equal to 0.0 —: ``MV_F64_ORD`` has NaN
+right but puts -0.0 below 0.0, so such a pick's K slot reads a copy of y with -0.0 replaced by 0.0 (``pick_y_key``) and
+is not shared with MAX(y), which keeps -0.0.  first / last have the partial state "v" (``distagg._partials``), its
+validity taken from V, so N ranks merge them like the paned path; max_by / min_by have no mergeable partial: like a
+distinct count they are tried here and nowhere else (``query._paned_aggregate``), and take the generic path when the
+ring declines, when the statement is not cacheable, or over a partitioned view at N ranks.
+
 **One answer, one plan entry per aggregate.**  Every layout is answered by the same call, ``dxa_win_answer``
 (combine, one distinct fold per pair state, keep, compaction, output rows), and its complete blocks are combined by
 ``dxa_win_combine_block``; the families differ only in what they hand over — the pair states' folds, ``m2desc``,
-``momdesc``, ``lodesc``, each 0 when the layout has none — and the absent descriptors pick the ``win_combine_kernel``
-instantiation without that branch, so a layout without X issues the launches it would issue if X did not exist
-(tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate once, where its
-slots are chosen: its ``plan`` entry, its finishing recipe and its partial states, all in slot terms; one pass after
-packing turns slots into words.  Adding an aggregate means one arm there (and, for a new kind of word, its kernels).
+``momdesc``, ``lodesc``, ``pickdesc``, each 0 when the layout has none — and the absent descriptors pick the
+``win_combine_kernel`` instantiation without that branch, so a layout without X issues the launches it would issue if
+X did not exist (tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate
+once, where its slots are chosen: its ``plan`` entry, its finishing recipe and its partial states, all in slot terms;
+one pass after packing turns slots into words.  Adding an aggregate means one arm there (and, for a new kind of word,
+its kernels).
 """
 from __future__ import annotations
 
@@ -131,8 +167,8 @@ from ..ops import native as N
 from ..ops.groupby import (_DEC_KEY_MAX, _DEC_KEY_MIN, _DEC_SUM, _F_AVG, _F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP,
                            _F_DEC_AVG, _F_DEC_MM, _F_DEC_SUM, _F_F64, _F_F64_ORD, _F_HI, _F_I64, _F_KURT, _F_NOT,
                            _F_SKEW, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64, _MA_LOKEY, _MA_M2,
-                           _MA_MAX, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64,
-                           _MV_NOT)
+                           _MA_MAX, _MA_MOM, _MA_PICK_RANK, _MA_PICK_VAL, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT,
+                           _MV_F64, _MV_F64_ORD, _MV_I64, _MV_NOT, _PICK_LAST, _PICK_USED)
 from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from . import decimal as Dec
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
@@ -149,9 +185,11 @@ MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per st
 MAX_MOMENTS = 8                   # skewness / kurtosis arguments plus corr / covar pairs (window_ring.hip kMaxMomArgs)
 MAX_DECIMAL = 8                   # decimal sum arguments plus two-lane decimal MIN / MAX (window_ring.hip kMaxDecJobs)
 SUM_PRECISION = 28                # SUM / AVG of decimal(p, s) is answered here for p up to this (``plan_layout``)
+MAX_PICK = 8                      # different rank jobs, and different payload jobs, of first / last / max_by / min_by
+                                  # per statement (window_ring.hip kMaxPickJobs)
 _ANSWER = [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p]    # ring … out_idx
-# m2desc, its host copy, momdesc, its host copy, lodesc, its host copy (0: the layout has none)
-_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p]
+# m2desc, its host copy, momdesc, its host copy, lodesc, its host copy, pickdesc, its host copy (0: the layout has none)
+_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p]
 N.register_sigs({
     "dxa_win_sizes": [N.c_p],
     "dxa_win_emit_size": [],
@@ -161,6 +199,8 @@ N.register_sigs({
     "dxa_win_mom_size": [],
     "dxa_win_dec_size": [],
     "dxa_win_dec": [N.c_p, N.c_p],
+    "dxa_win_pick_size": [],
+    "dxa_win_pick": [N.c_p, N.c_p],
     "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
     "dxa_win_insert_fused": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_p, N.c_p, N.c_p],
     "dxa_win_m2": [N.c_p, N.c_p],
@@ -186,7 +226,21 @@ _MOMENTS = {"skewness": _F_SKEW, "kurtosis": _F_KURT, "covar_pop": _F_COVAR_POP,
             "corr": _F_CORR}
 _PAIRED = ("covar_pop", "covar_samp", "corr")
 _NUMERIC = ("byte", "short", "int", "long", "double", "float")
+# row picks: x of one row of the group — the first or last in the window's row order, or the one with the extreme y
+_PICKS = ("first", "last", "max_by", "min_by")
+_PICKABLE = (*_NUMERIC, "boolean", "timestamp", "date")      # (and decimal(p, s), p ≤ 18): one 64-bit word per value
+_PICK_ALIAS = {"first_value": "first", "last_value": "last"}
 _SUPPORTED = {"count", "sum", "min", "max", "avg", "mean", "count_if", *_VARIANCE, *_BOOL, *_MOMENTS}
+# The row picks are eligible only for a caller that passes the combine its slots in the window's row order, and says so
+# (``_requests(aggs, picks=True)``; ``dense_answer`` does): the first two have a mergeable partial state, the keyed
+# ones have none and only the ring answers them (as it does COUNT(DISTINCT x))
+_RING_ONLY = ("max_by", "min_by")
+
+
+def pick_y_key(y):
+    """The argument key of a double order key y of max_by / min_by with -0.0 replaced by 0.0 (``DenseWindow.accumulate``
+    builds the column): the K slot of such a pick reads it, so its zeros tie as they do in ``query._arg_extreme``."""
+    return ("pick_y", y.key())
 
 
 def pair_keys(x, y):
@@ -257,6 +311,22 @@ class _DecArgs(ctypes.Structure):
                 ("nargs", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class _PickRank(ctypes.Structure):
+    _fields_ = [("y", ctypes.c_void_p), ("yvalid", ctypes.c_void_p), ("kind", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("r", ctypes.c_int32), ("last", ctypes.c_int32)]
+
+
+class _PickVal(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("xvalid", ctypes.c_void_p), ("r", ctypes.c_int32), ("p", ctypes.c_int32),
+                ("v", ctypes.c_int32), ("last", ctypes.c_int32)]
+
+
+class _PickArgs(ctypes.Structure):
+    _fields_ = [("rank", _PickRank * MAX_PICK), ("val", _PickVal * MAX_PICK), ("gid", ctypes.c_void_p),
+                ("row", ctypes.c_void_p), ("scal", ctypes.c_void_p), ("n", ctypes.c_int64), ("gcap", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("nrank", ctypes.c_int32), ("nval", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -271,7 +341,8 @@ def _sizes() -> List[int]:
                 N.lib().dxa_win_pairfold_size() != ctypes.sizeof(_PairFolds) or \
                 N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args) or \
                 N.lib().dxa_win_mom_size() != ctypes.sizeof(_MomArgs) or \
-                N.lib().dxa_win_dec_size() != ctypes.sizeof(_DecArgs):
+                N.lib().dxa_win_dec_size() != ctypes.sizeof(_DecArgs) or \
+                N.lib().dxa_win_pick_size() != ctypes.sizeof(_PickArgs):
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
@@ -280,7 +351,7 @@ class Ineligible(Exception):
     """The statement (or this batch) is answered by the paned path."""
 
 
-def _requests(aggs: Dict):
+def _requests(aggs: Dict, picks: bool = False):
     """[(agg key, func, arg expr or None)] or Ineligible.  ``COUNT(DISTINCT x)`` with one argument is the func
     "dcount"; every other DISTINCT aggregate is ineligible, and so are more than ``MAX_DISTINCT`` different
     distinct arguments.  The variance family keeps its name (``_VARIANCE``), ``bool_and`` / ``every`` are "min" and
@@ -289,14 +360,19 @@ def _requests(aggs: Dict):
     ``covar_pop`` / ``covar_samp`` (two: the arg entry is the tuple (x, y)) keep their names too; each different
     argument or pair is one job of the pane's moment pass, and more than ``MAX_MOMENTS`` of them are ineligible.  The
     M2 words they need (skewness / kurtosis: of the argument; corr: of both masked columns of the pair) count as
-    variance arguments."""
+    variance arguments.  ``first`` / ``last`` (one argument; ``first_value`` / ``last_value`` are the
+    same funcs, and the two-argument ``first(x, true)`` stays ineligible under its own name) and ``max_by`` /
+    ``min_by`` (two: the arg entry is the tuple (x, y)) keep their names — all four only with ``picks``, which promises
+    that the combine gets its slots in the window's row order, as ``_enqueue`` passes them; more than ``MAX_PICK``
+    different rank jobs (first, last, and one per direction and y) or payload jobs (rank job and x) are ineligible."""
     out = []
     dargs = set()
     vargs = set()
     margs = set()
+    pranks, pvals = set(), set()
     for ak, call in aggs.items():
         name = call.name
-        if name not in _SUPPORTED:
+        if name not in _SUPPORTED and not (picks and _PICK_ALIAS.get(name, name) in _PICKS):
             raise Ineligible(name)
         if call.distinct:
             if name != "count" or call.star or len(call.args) != 1:
@@ -322,6 +398,18 @@ def _requests(aggs: Dict):
             if len(margs) > MAX_MOMENTS or len(vargs) > MAX_VARIANCE:
                 raise Ineligible("too many moment arguments")
             out.append((ak, name, tuple(call.args) if name in _PAIRED else call.args[0]))
+            continue
+        name = _PICK_ALIAS.get(name, name)
+        if name in _PICKS:
+            keyed = name in _RING_ONLY
+            if len(call.args) != (2 if keyed else 1):
+                raise Ineligible(call.name)
+            rank = (name, call.args[1].key()) if keyed else (name,)
+            pranks.add(rank)
+            pvals.add((rank, call.args[0].key()))
+            if len(pranks) > MAX_PICK or len(pvals) > MAX_PICK:
+                raise Ineligible("too many pick arguments")
+            out.append((ak, name, tuple(call.args) if keyed else call.args[0]))
             continue
         if len(call.args) != 1:
             raise Ineligible(name)
@@ -396,7 +484,14 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     per ``plan`` entry (first ``fin`` row, rows), and a decimal partial state in ``pfin`` is a list of two recipes.
     ``decargs`` [(arg key, job kind, word 0, word 1, word 2)] lists win_dec_kernel's jobs.  ``lodesc`` / ``decargs``
     are absent from a layout without such words.  The variance and moment families take a decimal argument as the
-    double ``decimal.to_double`` gives (as Spark casts it)."""
+    double ``decimal.to_double`` gives (as Spark casts it).
+
+    first / last / max_by / min_by (module docstring): a rank slot in an ``MA_PICK_RANK`` line, a payload and a
+    validity slot per payload argument in ``MA_PICK_VAL`` lines, all with value kind -1, and for the keyed ones the
+    ``MA_MAX`` slot of y.  ``pickdesc`` (per word of those lines: R word | (K word + 1) << 8 | last << 16 | in use <<
+    17) is win_combine_kernel's, ``pickargs`` = (rank jobs [(K argument key or None, K value kind, K word or -1, R
+    word, last)], payload jobs [(x key, R word, P word, V word, last)]) dxa_win_pick's, ``pick_x`` maps a pick's agg key
+    to its payload argument.  All three are absent from a layout without picks."""
     # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
     slots, keyed = [], {}
 
@@ -414,6 +509,10 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     m2_of = {}                      # M2 slot → (count slot, sum slot) of the same argument
     mom_of = {}                     # M3 / M4 / Cxy slot → (kind, the slots its combine reads)
     mom_jobs = {}                   # argument key or pair keys → [x, y, count, sum x, sum y, word-0, word-1 slot]
+    pick_of = {}                    # R / P / V slot of a row pick → (its R slot, its K slot or None, last among equals)
+    pick_ranks = {}                 # R slot → (K slot's argument key or None, its value kind, K slot or None, last)
+    pick_vals = {}                  # P slot → (x key, R slot, V slot, last)
+    pick_x = {}                     # agg key of a pick → its payload argument's key
 
     def agg(ak, kind, s, c, dt, fkind, states, ops=(), f64=None):
         """One aggregate, described once and in slot terms (mapped to words after packing): its ``plan`` entry, its
@@ -448,6 +547,39 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
             # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
             # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
             agg(ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None, _F_COUNT, None)
+            continue
+        if func in _PICKS:
+            # a row pick: a rank word R (which row of the pane wins; shared by every pick of the same kind and y), and
+            # per payload argument x that row's 64 bits P and its validity V as a double 1.0 / 0.0 — a count word to
+            # win_emit_kernel, whose rule "count > 0 → valid" then makes a NULL x (or no row) a NULL result.  max_by /
+            # min_by: and the key word K, the ordinary MAX slot of y (complemented for min_by) that MAX(y) / MIN(y) of
+            # the same statement share; a double y is keyed by a copy with -0.0 → 0.0 (``pick_y_key``), which only
+            # the picks read, so that equal zeros tie as in ``query._arg_extreme``
+            x, y = arg if isinstance(arg, tuple) else (arg, None)
+            for a in (x,) if y is None else (x, y):
+                dt = arg_types[a.key()][0]
+                if not (dt in _PICKABLE or (is_decimal(dt) and dt.narrow)):
+                    raise Ineligible("argument type")
+            xdt = arg_types[x.key()][0]
+            last = func == "last"
+            ks = yk = kkind = None
+            rank = (func,)
+            if y is not None:
+                is_fy = arg_types[y.key()][0] in ("float", "double")
+                yk = pick_y_key(y) if is_fy else y.key()
+                kkind = (_MV_F64_ORD if is_fy else _MV_I64) | (_MV_NOT if func == "min_by" else 0)
+                ks = slot((func[:3], yk), kkind, _MA_MAX)
+                rank = (func, yk)
+            r = slot(("pickr", rank), -1, _MA_PICK_RANK)
+            pv = slot(("pickp", (rank, x.key())), -1, _MA_PICK_VAL)
+            vv = slot(("pickv", (rank, x.key())), -1, _MA_PICK_VAL)
+            for sl in (r, pv, vv):
+                pick_of[sl] = (r, ks, last)
+            pick_ranks[r] = (yk, kkind, ks, last)
+            pick_vals[pv] = (x.key(), r, vv, last)
+            pick_x[ak] = x.key()
+            agg(ak, "pick", pv, vv, xdt, _F_I64, {"v": (_F_I64, pv, vv)} if y is None else None,
+                f64=xdt in ("float", "double"))
             continue
         if func in _PAIRED:
             # (n, Σx, Σy, Cxy) over the rows where both arguments are non-null: count and sums of the pair's masked
@@ -550,7 +682,9 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     order, line_ops = [], []
     if len(dec_jobs) > MAX_DECIMAL:
         raise Ineligible("too many decimal arguments")
-    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM, _MA_LOKEY):
+    if len(pick_ranks) > MAX_PICK or len(pick_vals) > MAX_PICK:
+        raise Ineligible("too many pick arguments")
+    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM, _MA_LOKEY, _MA_PICK_RANK, _MA_PICK_VAL):
         mine = [i for i, sl in enumerate(slots) if sl[2] == op]
         for k in range(0, len(mine), 8):
             chunk = mine[k:k + 8]
@@ -590,6 +724,20 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         for lo, hi in lo_of.items():
             lodesc[where[lo]] = where[hi] | 1 << 16
         out["lodesc"] = lodesc
+    if pick_of:
+        # per word of the two pick ops: its R word | (its K word + 1) << 8 | last << 16 | in use (win_combine_kernel);
+        # the rank jobs [(K argument key or None, K value kind, K word, R word, last)] and the payload jobs [(x key, R
+        # word, P word, V word, last)] of win_pick_kernel / win_pick_gather_kernel
+        pickdesc = [0] * stride
+        for sl, (r, ks, last) in pick_of.items():
+            pickdesc[where[sl]] = where[r] | (0 if ks is None else where[ks] + 1) << 8 | (_PICK_LAST if last else 0) | \
+                _PICK_USED
+        out["pickdesc"] = pickdesc
+        out["pick_x"] = pick_x
+        out["pickargs"] = ([(yk, kk or 0, -1 if ks is None else where[ks], where[r], int(last))
+                            for r, (yk, kk, ks, last) in pick_ranks.items()],
+                           [(xk, where[r], where[pv], where[vv], int(last))
+                            for pv, (xk, r, vv, last) in pick_vals.items()])
     if mom_of:
         # per op-4 word: kind << 24 | the words it reads, 6 bits each (win_combine_kernel); per argument or pair the
         # words of its job in the pane's moment pass (win_mom_kernel)
@@ -735,6 +883,9 @@ class DenseWindow:
         self.m2desc_t = self.m2desc_dev = None  # with variance arguments: win_combine_kernel's M2 descriptor
         self.momdesc_t = self.momdesc_dev = None        # with op-4 lines: its M3 / M4 / Cxy descriptor
         self.lodesc_t = self.lodesc_dev = None          # with low-key lines (two-lane decimal MIN / MAX): the high words
+        self.pickdesc_t = self.pickdesc_dev = None      # with row picks: the R and K word of each pick word
+        # row picks combine slots by their place in the window's row order (``_enqueue``)
+        self.has_picks = any(func in _PICKS for _, func, _arg in reqs)
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
         self.free = list(range(ring_slots))    # free pane slots (a heap: the lowest is taken first)
         self.disabled = False
@@ -813,17 +964,25 @@ class DenseWindow:
             raise Ineligible("memory") from None
         L = plan_layout(self.reqs, {k: (c.dtype, c.data.dtype == torch.float64) for k, c in args.items()})
         L["pspec_of"] = self._partial_spec
+        # payload arguments stored as float32: their picks are kept as doubles and narrowed again in ``_finals``
+        self.f32_args = {k for k, c in args.items() if c.data.dtype == torch.float32}
         self.stride = L["stride"]
         self.layout = L
         # agg_multi (host ``line_ops_t``) sees an M2 line as an f64 add line of unused slots, so every pane starts
         # its M2 words at 0.0; the ring kernels (``line_ops_dev``) see MA_M2
-        # and a low-key line as a max line of unused slots, so every pane starts its low key words at INT64_MIN
-        self.line_ops_t = torch.tensor([_MA_ADD_F64 if op in (_MA_M2, _MA_MOM) else _MA_MAX if op == _MA_LOKEY else op
-                                        for op in L["line_ops"]], dtype=torch.int32)
+        # and a low-key line as a max line of unused slots, so every pane starts its low key words at INT64_MIN; so do
+        # a pick's rank words, and its payload and validity words start at 0 as unused u64 add words
+        host_op = {_MA_M2: _MA_ADD_F64, _MA_MOM: _MA_ADD_F64, _MA_LOKEY: _MA_MAX, _MA_PICK_RANK: _MA_MAX,
+                   _MA_PICK_VAL: _MA_ADD_U64}
+        self.line_ops_t = torch.tensor([host_op.get(op, op) for op in L["line_ops"]], dtype=torch.int32)
         self.line_ops_dev = torch.tensor(L["line_ops"], dtype=torch.int32).to(self.device)
         self.m2desc_t = self.m2desc_dev = None
         self.momdesc_t = self.momdesc_dev = None
         self.lodesc_t = self.lodesc_dev = None
+        self.pickdesc_t = self.pickdesc_dev = None
+        if "pickdesc" in L:
+            self.pickdesc_t = torch.tensor(L["pickdesc"], dtype=torch.int32)
+            self.pickdesc_dev = self.pickdesc_t.to(self.device)
         if "lodesc" in L:
             self.lodesc_t = torch.tensor(L["lodesc"], dtype=torch.int32)
             self.lodesc_dev = self.lodesc_t.to(self.device)
@@ -973,7 +1132,14 @@ class DenseWindow:
                         c.data.dim() != (2 if is_decimal(c.dtype) and not c.dtype.narrow else 1):
                     raise Ineligible("argument type")
                 args[a.key()] = c
-            if isinstance(arg, tuple) and pair_keys(*arg)[0] not in args:
+            if func in ("max_by", "min_by"):
+                # a double order key: the copy with -0.0 → 0.0 that the pick's K slot and win_pick_kernel read
+                y = args[arg[1].key()]
+                if y.dtype in ("float", "double") and pick_y_key(arg[1]) not in args:
+                    d = y.data.to(torch.float64)
+                    args[pick_y_key(arg[1])] = PrimColumn("double", torch.where(d == 0.0, torch.zeros_like(d), d),
+                                                          y.valid)
+            elif isinstance(arg, tuple) and pair_keys(*arg)[0] not in args:
                 # a pair's columns: the arguments' data under the validity "both non-null", built once per pane
                 x, y = args[arg[0].key()], args[arg[1].key()]
                 both = x.valid if y.valid is None else y.valid if x.valid is None else \
@@ -1008,7 +1174,9 @@ class DenseWindow:
                N.ptr(self.htab), self.hcap, N.ptr(self.gid_of_slot), N.ptr(self.scal), N.ptr(gid), st)
         spec, hold = [], [gid, keep, kc]
         xs = {}                         # variance arguments: the (float64 values, validity) their sum slot reads
-        for i in L["order"][:L["nslots"]]:
+        # with row picks: word → the (values, validity) agg_multi reads for it (win_pick_kernel reads a K word's)
+        fed = {} if "pickargs" in L else None
+        for pos, i in enumerate(L["order"][:L["nslots"]]):
             if i is None:
                 spec += [0, 0, -1]
                 continue
@@ -1044,6 +1212,8 @@ class DenseWindow:
             hold += [d, v]
             if key[0] == "sumf":
                 xs[key[1]] = (d, v)
+            if fed is not None:
+                fed[pos] = (d, v)
             spec += [d.data_ptr(), 0 if v is None else v.data_ptr(), kind]
         spec_t = torch.tensor(spec, dtype=torch.int64)
         ring_ptr = self.ring[slot_idx].data_ptr()
@@ -1078,16 +1248,41 @@ class DenseWindow:
                 hold += [d, v]
                 m.a[k] = _DecJob(d.data_ptr(), 0 if v is None else v.data_ptr(), d.dim(), kind, w0, w1, w2, 0)
             N.call("dxa_win_dec", self._second_pass(m, len(L["decargs"]), gid, ring_ptr, n), st)
+        if L.get("pickargs") and n > 0:
+            # the pick pass: the rank words from the finished key words (win_pick_kernel reads the very arrays agg_multi
+            # read for them), then every payload argument's bits and validity at the winning rows, all jobs of the
+            # statement in two launches of one call
+            m = _PickArgs()
+            ranks, vals = L["pickargs"]
+            for k, (yk, kind, kw, rw, last) in enumerate(ranks):
+                d, v = fed[kw] if yk is not None else (None, None)
+                m.rank[k] = _PickRank(0 if d is None else d.data_ptr(), 0 if v is None else v.data_ptr(), kind, kw, rw,
+                                      last)
+            bits = {}
+            for k, (xk, rw, pw, vw, last) in enumerate(vals):
+                if xk not in bits:
+                    c = args[xk]
+                    d = c.data
+                    d = d.to(torch.float64) if d.dtype == torch.float32 else d if d.dtype in (
+                        torch.int64, torch.float64) else d.to(torch.int64)
+                    v = N.u8(c.valid)
+                    bits[xk] = (d.contiguous(), None if v is None else v.contiguous())
+                d, v = bits[xk]
+                m.val[k] = _PickVal(d.data_ptr(), 0 if v is None else v.data_ptr(), rw, pw, vw, last)
+            hold.append(bits)
+            m.gid, m.row, m.scal, m.n = gid.data_ptr(), ring_ptr, self.scal.data_ptr(), n
+            m.gcap, m.stride, m.nrank, m.nval = self.gcap, self.stride, len(ranks), len(vals)
+            N.call("dxa_win_pick", ctypes.addressof(m), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
 
     def _descs(self):
         """The combine's descriptors for ``dxa_win_answer`` / ``dxa_win_combine_block``: ``m2desc`` on the device and
-        on the host, ``momdesc`` and ``lodesc`` likewise; 0 where the layout has none, which picks the combine without
-        that branch."""
+        on the host, ``momdesc``, ``lodesc`` and ``pickdesc`` likewise; 0 where the layout has none, which picks the
+        combine without that branch."""
         return (N.ptr(self.m2desc_dev), N.ptr(self.m2desc_t), N.ptr(self.momdesc_dev), N.ptr(self.momdesc_t),
-                N.ptr(self.lodesc_dev), N.ptr(self.lodesc_t))
+                N.ptr(self.lodesc_dev), N.ptr(self.lodesc_t), N.ptr(self.pickdesc_dev), N.ptr(self.pickdesc_t))
 
     def _second_pass(self, m, nargs: int, gid: torch.Tensor, ring_ptr: int, n: int) -> int:
         """The fields ``_M2Args`` and ``_MomArgs`` share, after their jobs: the pane's group ids and ring slot → the
@@ -1107,7 +1302,8 @@ class DenseWindow:
         is first complete in a window; reused until a member leaves).  ``mem``: the members' slot entries."""
         # members by the identity of their slot entries: an entry is made once per pane assignment and lives in
         # slot_of while the pane is retained; the cache holds the entries too, so no id is reused while cached
-        members = frozenset(map(id, mem))
+        # (row picks: in the order given — the window's row order — and combined again should that order change)
+        members = tuple(map(id, mem)) if self.has_picks else frozenset(map(id, mem))
         ent = self.blocks.get(bid)
         if ent is not None and ent[0] == members:
             return ent[1]
@@ -1116,7 +1312,7 @@ class DenseWindow:
         if not free:
             raise Ineligible("block slots")
         dst = free[0]
-        member_slots = [e[0] for e in sorted(mem, key=lambda e: e[3])]
+        member_slots = [e[0] for e in (mem if self.has_picks else sorted(mem, key=lambda e: e[3]))]
         slots_dev = self._dev_slots(member_slots)
         st = N.stream_handle(self.device)
         N.call("dxa_win_combine_block", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(member_slots),
@@ -1222,6 +1418,8 @@ class DenseWindow:
             else:
                 finals[ak] = PrimColumn(dt, v.view(torch.float64) if f64 else v.to(torch.bool) if dt == "boolean"
                                         else v, ok)
+                if L.get("pick_x", {}).get(ak) in self.f32_args:
+                    finals[ak] = PrimColumn(dt, finals[ak].data.to(torch.float32), ok)
         return finals
 
     def _emit_args(self, fin):
@@ -1276,6 +1474,8 @@ class DenseWindow:
                     got[nm] = PrimColumn(like.dtype, v)
                 elif isinstance(like, PrimColumn) and like.data.dtype == torch.float64:
                     got[nm] = PrimColumn(like.dtype, v.view(torch.float64), ok)
+                elif isinstance(like, PrimColumn) and like.data.dtype == torch.float32:     # (a float32 pick)
+                    got[nm] = PrimColumn(like.dtype, v.view(torch.float64).to(torch.float32), ok)
                 elif like.dtype == "boolean":
                     got[nm] = PrimColumn(like.dtype, v.to(torch.bool), ok)
                 else:
@@ -1326,7 +1526,8 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
         return None
     if not sel.group_by and not distinct:   # a global statement without a distinct count keeps the paned path
         return None
-    if distinct and partial_proto is not None:      # a distinct count has no mergeable partial
+    # a distinct count has no mergeable partial, nor have max_by / min_by
+    if partial_proto is not None and (distinct or any(c.name in ("max_by", "min_by") for c in aggs.values())):
         return None
     states = store.__dict__.setdefault("_dense", {})
     state = states.get(fp)
@@ -1339,7 +1540,7 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
         if state is None:
             iv = max(1, store.interval_us)
             panes = store.conf.max_window_us // iv + store.conf.watermark_us // iv + 4
-            state = states[fp] = DenseWindow(dev, _requests(aggs), max(panes, len(pieces) + 2),
+            state = states[fp] = DenseWindow(dev, _requests(aggs, picks=True), max(panes, len(pieces) + 2),
                                              global_form=not sel.group_by)
         state._rebuilt = set()
         proto = pieces[0][0].table
@@ -1411,6 +1612,7 @@ def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defe
     slots = []
     span = BLOCK * max(1, store.interval_us)
     by_block: Dict[int, list] = {}
+    seq = [] if state.has_picks else None          # row picks: the window's row order — scratch slots and entries
     for pane, full in pieces:
         if full:                                   # (pieces' "full" includes every row having a timestamp)
             ent = slot_of.get(pane.key)
@@ -1429,6 +1631,8 @@ def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defe
                 by_block[ent[2]] = [ent]
             else:
                 mem.append(ent)
+            if seq is not None:
+                seq.append(ent)
         else:
             # a pane only partly inside the window: its in-range rows, re-aggregated into a scratch slot
             if not scratch:
@@ -1436,10 +1640,15 @@ def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defe
             sl = scratch.pop(0)
             state.accumulate(t.clipped(pane), sl, alias, sel.where, gexprs, ctx)
             slots.append(sl)
+            if seq is not None:
+                seq.append(sl)
     # complete blocks of BLOCK consecutive panes: one pre-combined slot each (the per-batch combine then reads
     # ~20 block slots and the loose panes at the window's edges instead of 300 pane slots)
     for bid in [b for b in state.blocks if b not in by_block]:
         del state.blocks[bid]
+    if seq is not None:
+        return state.answer(_ordered_slots(state, seq, by_block), partial_proto,
+                            defer=defer and partial_proto is None)
     for bid, mem in by_block.items():
         if len(mem) == BLOCK:
             slots.append(state.block_slot(bid, mem))
@@ -1447,6 +1656,37 @@ def _enqueue(state, t, pieces, sel, alias: str, gexprs, ctx, partial_proto, defe
             state.blocks.pop(bid, None)
             slots.extend(e[0] for e in mem)
     return state.answer(slots, partial_proto, defer=defer and partial_proto is None)
+
+
+def _ordered_slots(state, seq: list, by_block: Dict[int, list]) -> List[int]:
+    """The combine's slots of a layout with row picks, in the window's row order (that of ``PanedTable.pieces``, which
+    the materialised view concatenates in): ``seq`` holds, in that order, the scratch slots of the clipped panes and
+    the slot entries of the whole ones.  A complete block goes in as its pre-combined slot where its members stand
+    together — in the order they stand in, which is the order ``block_slot`` combines them in; the block that holds
+    the current pane does not (the current pane comes first, the block's older members after the panes in between),
+    so its members go in one by one, as those of an incomplete block do."""
+    slots: List[int] = []
+    used = set()
+    k = 0
+    while k < len(seq):
+        ent = seq[k]
+        if not isinstance(ent, tuple):
+            slots.append(ent)
+            k += 1
+            continue
+        bid = ent[2]
+        run = k + 1
+        while run < len(seq) and isinstance(seq[run], tuple) and seq[run][2] == bid:
+            run += 1
+        if run - k == BLOCK and len(by_block[bid]) == BLOCK:
+            slots.append(state.block_slot(bid, seq[k:run]))
+            used.add(bid)
+        else:
+            slots.extend(e[0] for e in seq[k:run])
+        k = run
+    for bid in [b for b in state.blocks if b not in used]:
+        del state.blocks[bid]
+    return slots
 
 
 class _Disabled:

@@ -33,8 +33,10 @@
 // AVG, divides it exactly with HALF_UP rounding); MIN / MAX of a two-lane decimal keep a two-word order key, the hi
 // word an ordinary MA_MAX word and the lo word in a line of the combine op MA_LOKEY (described by ``lodesc``).
 // Every layout goes through the same two host entry points, dxa_win_answer (steps 3-5) and dxa_win_combine_block; the
-// descriptors a layout passes (none, m2desc, m2desc + momdesc; with or without lodesc) pick the win_combine_kernel
-// instantiation.
+// descriptors a layout passes (none, m2desc, m2desc + momdesc; with or without lodesc; with or without pickdesc) pick
+// the win_combine_kernel instantiation.
+// first / last / max_by / min_by keep a row pick per pane and group (a rank word, the picked row's value and its
+// validity; win_pick_kernel and win_pick_gather_kernel fill them) and slots combine by their place in the window.
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -61,6 +63,18 @@ enum : int32_t { MOM_M3 = 1, MOM_M4 = 2, MOM_CXY = 3 };
 // ``lodesc`` names per word its high word (index | 1 << 16; 0: padding).  agg_multi sees such a line as MA_MAX with
 // unused slots (every pane starts it at INT64_MIN), win_dec_kernel fills it after the high word is finished.
 enum : int32_t { MA_LOKEY = 5 };
+// Row picks (first / last / max_by / min_by): per pane and group the state is "which row wins" and that row's value.
+//   MA_PICK_RANK lines hold rank words R: identity INT64_MIN ("no row"), else a monotone map of the winning row's index
+//                in its pane — INT64_MAX − i where the smallest index wins (first, max_by, min_by: ties on the key keep
+//                the first row), i where the largest wins (last).  win_pick_kernel fills them by a 64-bit max.
+//   MA_PICK_VAL  lines hold, per payload argument x, a word P = the 64 bits of x of the winning row and a word V =
+//                1.0 / 0.0 (x non-NULL / NULL there), both 0 without a row; win_pick_gather_kernel fills them.
+// max_by / min_by also have a key word K, an ordinary MA_MAX word agg_multi fills from y (complemented for min_by).
+// ``pickdesc`` [stride] names per word of these lines its R word (bits 0-7), its K word + 1 (bits 8-15; 0: not
+// keyed), "last among equals" (bit 16) and "in use" (bit 17; 0: padding).  Ranks of different panes do not compare:
+// slots are combined by their place in the ``slots`` array (the window's row order), see win_combine_kernel.
+// agg_multi sees both kinds of line as unused words (INT64_MIN and 0).
+enum : int32_t { MA_PICK_RANK = 6, MA_PICK_VAL = 7 };
 
 // same layout as hash_groupby.hip's KeyCols (built by dxa/ops/hashing.py key_cols)
 struct KeyCol {
@@ -125,7 +139,13 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
 // combines as the max of the slots' words over the slots whose high word equals the max of the high words, so the
 // (high, low) pair is the lexicographic max; slots that are all the identity (INT64_MIN twice) give the identity.
 // Without kKey the branch is compiled out.
-template <bool kBlock, bool kM2, bool kMom, bool kKey>
+// ``kPick``: the layout has MA_PICK_RANK / MA_PICK_VAL lines and ``pickdesc`` [stride] names each of their words' R
+// word and K word.  Such a word is taken from one slot: among the slots, in the order of ``slots``, whose R word is not
+// the identity — and, for a keyed pick, whose K word equals the max of the K words — the first one, or the last one
+// for ``last``.  R, P and V of one pick choose the same slot, so a block slot holds a consistent (K, R, P, V) again
+// (its R only says "has a row": nothing decodes a combined rank).  No such slot gives the line's identity.  Without
+// kPick the branch is compiled out.
+template <bool kBlock, bool kM2, bool kMom, bool kKey, bool kPick>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
                                                           int32_t nslots_in, int32_t stride,
@@ -134,7 +154,8 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
                                                           int32_t fixed_rows, unsigned long long* __restrict__ out,
                                                           const int32_t* __restrict__ m2desc,
                                                           const int32_t* __restrict__ momdesc,
-                                                          const int32_t* __restrict__ lodesc) {
+                                                          const int32_t* __restrict__ lodesc,
+                                                          const int32_t* __restrict__ pickdesc) {
   int32_t ng = scal[0];
   if (ng > gcap) ng = gcap;
   const int64_t held = (int64_t)ng * stride;
@@ -222,6 +243,27 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
         acc = v > acc ? v : acc;
       }
       out[idx] = (unsigned long long)acc;
+    } else if (kPick && (op == MA_PICK_RANK || op == MA_PICK_VAL)) {
+      const int32_t dsc = pickdesc[w];
+      const int ns_in = dsc ? nslots : 0;
+      const int64_t r_at = idx - w + (dsc & 0xff);
+      const int kw = (dsc >> 8) & 0xff;
+      const int64_t k_at = idx - w + kw - 1;
+      const bool last = (dsc >> 16) & 1;
+      const long long none = (long long)0x8000000000000000ull;
+      long long top = none;
+      for (int s = 0; kw && s < ns_in; ++s) {
+        const long long k = (long long)ring[(int64_t)slots[s] * slot_words + k_at];
+        top = k > top ? k : top;
+      }
+      unsigned long long acc = op == MA_PICK_RANK ? 0x8000000000000000ull : 0ull;
+      for (int s = 0; s < ns_in; ++s) {
+        const int64_t base = (int64_t)slots[s] * slot_words;
+        if ((long long)ring[base + r_at] == none || (kw && (long long)ring[base + k_at] != top)) continue;
+        acc = ring[base + idx];
+        if (!last) break;
+      }
+      out[idx] = acc;
     } else {
       long long acc = (long long)0x8000000000000000ull;
       for (int s = 0; s < nslots; ++s) {
@@ -493,6 +535,108 @@ __global__ __launch_bounds__(256) void win_dec_kernel(const DecArgs m) {
       }
     }
     __syncthreads();
+  }
+}
+
+// 2e. the same second pass for row picks, in two launches.
+// win_pick_kernel: every rank job of the statement, one after the other through one LDS u64 array (8 KB).  A row that
+// counts puts its rank (INT64_MAX − i: the smallest index wins; i for ``last``) into its group's R word by a 64-bit
+// max.  Rows of the dump row (WHERE-filtered or dictionary-full) and ids outside [0, gcap) never count.  For a keyed
+// job (max_by / min_by) agg_multi has finished the group's K word from the same ``y`` array, so a row counts when its
+// y is non-NULL and its key — y itself, or hash_groupby.hip's f64_ordered(y) for a double (MV_F64_ORD), complemented
+// for min_by — equals K: the rows that tie on the extreme y, of which the smallest index wins.
+//   Order of a double y: query._arg_extreme sorts by ops/sort.py's order key, where NaN is the largest value, every
+//   NaN is the same value and -0.0 == 0.0.  f64_ordered agrees on NaN (one canonical NaN, the greatest) but puts
+//   -0.0 below 0.0, so the host hands both kernels a copy of y with -0.0 replaced by 0.0 (window_dense.py
+//   ``accumulate``): the zeros tie and the first row wins, as in _arg_extreme.
+// Ids below kM2LdsGroups go through LDS and are flushed with one global atomic per touched group and workgroup, the
+// others go straight to the row with non-returning 64-bit atomics.
+// win_pick_gather_kernel: a second launch, because R must be complete.  Threads stride over the groups in use (the
+// device's group counter, clamped to gcap: no host read); per payload job the row index is decoded from R and checked
+// against [0, n) before any load — the identity or a stale R never becomes an index — and x[row]'s 64 bits go into P,
+// 1.0 / 0.0 from x's validity into V.  A group without a row keeps the identities (R = INT64_MIN, P = V = 0).
+constexpr int kMaxPickJobs = 8;
+struct PickRank {
+  const long long* y;      // null: first / last (every row of the group counts)
+  const uint8_t* yvalid;
+  int32_t kind;            // keyed: the K slot's agg_multi value kind, MV_I64 (1) or MV_F64_ORD (3), | MV_NOT (4)
+  int32_t k;               // words of the slot row: K (keyed jobs) and R
+  int32_t r;
+  int32_t last;
+};
+struct PickVal {
+  const long long* x;      // the payload argument as 64-bit words
+  const uint8_t* xvalid;
+  int32_t r;               // words of the slot row: the rank word read, the payload and validity words written
+  int32_t p;
+  int32_t v;
+  int32_t last;            // how R maps to a row index
+};
+struct PickArgs {
+  PickRank rank[kMaxPickJobs];
+  PickVal val[kMaxPickJobs];
+  const int32_t* gid;
+  unsigned long long* row; // the ring slot: [gcap + 1][stride]
+  const int32_t* scal;     // the dictionary's status: scal[0] = groups in use
+  int64_t n;
+  int32_t gcap;
+  int32_t stride;
+  int32_t nrank;
+  int32_t nval;
+};
+
+// hash_groupby.hip's f64_ordered: the total order of doubles as signed integers, NaN canonical and greatest
+__device__ __forceinline__ long long pick_f64_ordered(double d) {
+  long long b = __double_as_longlong(d);
+  if (d != d) b = 0x7ff8000000000000ll;
+  return b >= 0 ? b : (b ^ 0x7fffffffffffffffll);
+}
+
+__global__ __launch_bounds__(256) void win_pick_kernel(const PickArgs m) {
+  __shared__ long long part[kM2LdsGroups];
+  constexpr long long kNone = (long long)0x8000000000000000ull;
+  const int32_t lds_groups = m.gcap < kM2LdsGroups ? m.gcap : kM2LdsGroups;
+  for (int k = 0; k < m.nrank; ++k) {
+    const PickRank a = m.rank[k];
+    for (int g = threadIdx.x; g < kM2LdsGroups; g += blockDim.x) part[g] = kNone;
+    __syncthreads();
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m.n; i += (int64_t)gridDim.x * blockDim.x) {
+      const int32_t g = m.gid[i];
+      if (g < 0 || g >= m.gcap) continue;
+      unsigned long long* r = m.row + (int64_t)g * m.stride;
+      if (a.y) {
+        if (a.yvalid && !a.yvalid[i]) continue;
+        long long key = (a.kind & 3) == 3 ? pick_f64_ordered(__longlong_as_double(a.y[i])) : a.y[i];
+        if (a.kind & 4) key = ~key;
+        if (key != (long long)r[a.k]) continue;
+      }
+      const long long rank = a.last ? (long long)i : 0x7fffffffffffffffll - (long long)i;
+      if (g < kM2LdsGroups) atomicMax(&part[g], rank);
+      else atomicMax((long long*)(r + a.r), rank);
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < lds_groups; g += blockDim.x)
+      if (part[g] != kNone) atomicMax((long long*)(m.row + (int64_t)g * m.stride + a.r), part[g]);
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void win_pick_gather_kernel(const PickArgs m) {
+  constexpr long long kNone = (long long)0x8000000000000000ull;
+  int32_t ng = m.scal[0];
+  if (ng > m.gcap) ng = m.gcap;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long* r = m.row + g * m.stride;
+    for (int k = 0; k < m.nval; ++k) {
+      const PickVal a = m.val[k];
+      const long long rank = (long long)r[a.r];
+      if (rank == kNone) continue;
+      // (unsigned: a stale word may hold anything, and the subtraction must not overflow)
+      const long long i = a.last ? rank : (long long)(0x7fffffffffffffffull - (unsigned long long)rank);
+      if (i < 0 || i >= m.n) continue;
+      r[a.p] = (unsigned long long)a.x[i];
+      r[a.v] = (unsigned long long)__double_as_longlong(a.xvalid && !a.xvalid[i] ? 0.0 : 1.0);
+    }
   }
 }
 
@@ -820,7 +964,8 @@ __global__ __launch_bounds__(256) void win_remap_slot_kernel(const unsigned long
     const int64_t p = idx / stride;
     const int w = (int)(idx - p * stride);
     const int op = line_op[w >> 3];
-    unsigned long long v = (op == MA_MAX_I64 || op == MA_LOKEY) ? 0x8000000000000000ull : 0ull;
+    const bool lowest = op == MA_MAX_I64 || op == MA_LOKEY || op == MA_PICK_RANK;      // (MA_PICK_VAL words start at 0)
+    unsigned long long v = lowest ? 0x8000000000000000ull : 0ull;
     if (p < live) v = src[out_idx[p] * stride + w];
     dst[idx] = v;
   }
@@ -997,7 +1142,8 @@ DXA_API int dxa_win_init(uint64_t* keys, int32_t* gid_of_slot, int64_t cap, void
 // A layout with MA_M2 lines passes ``m2desc`` [stride] on the device (win_combine_kernel) and ``m2desc_host``, the same
 // words for the bounds check here; one with MA_MOM lines also ``momdesc`` / ``momdesc_host``, and then ``m2desc`` is
 // required too (all zero without M2 lines).  A layout without such lines passes null for both pairs.  A layout with
-// MA_LOKEY lines passes ``lodesc`` / ``lodesc_host`` the same way, independently of the other two.
+// MA_LOKEY lines passes ``lodesc`` / ``lodesc_host`` the same way, independently of the other two, and one with
+// MA_PICK_RANK / MA_PICK_VAL lines ``pickdesc`` / ``pickdesc_host``, independently again.
 
 static bool m2desc_ok(const int32_t* host_desc, int32_t stride) {
   for (int w = 0; w < stride; ++w) {
@@ -1028,13 +1174,24 @@ static bool lodesc_ok(const int32_t* host_desc, int32_t stride) {
   return true;
 }
 
+// (the word indices are 8-bit fields: R, then K + 1 or 0; bit 16 "last", bit 17 "in use")
+static bool pickdesc_ok(const int32_t* host_desc, int32_t stride) {
+  if (stride > 255) return false;
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d && ((d >> 17) != 1 || (d & 0xff) >= stride || ((d >> 8) & 0xff) > stride)) return false;
+  }
+  return true;
+}
+
 static bool descs_ok(const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
                      const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
-                     int32_t stride) {
-  if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc) || !lodesc != !lodesc_host)
+                     const int32_t* pickdesc, const int32_t* pickdesc_host, int32_t stride) {
+  if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc) || !lodesc != !lodesc_host ||
+      !pickdesc != !pickdesc_host)
     return false;
   return (!m2desc || m2desc_ok(m2desc_host, stride)) && (!momdesc || momdesc_ok(momdesc_host, stride)) &&
-         (!lodesc || lodesc_ok(lodesc_host, stride));
+         (!lodesc || lodesc_ok(lodesc_host, stride)) && (!pickdesc || pickdesc_ok(pickdesc_host, stride));
 }
 
 static bool folds_ok(const PairFolds* pf, int32_t stride) {
@@ -1063,17 +1220,26 @@ static bool emit_ok(const EmitArgs& ea, int32_t stride) {
 template <bool kBlock>
 static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t stride, const int32_t* slots,
                            int32_t nslots, const int32_t* line_op, const int32_t* scal, unsigned long long* out,
-                           const int32_t* m2desc, const int32_t* momdesc, const int32_t* lodesc, hipStream_t s) {
+                           const int32_t* m2desc, const int32_t* momdesc, const int32_t* lodesc,
+                           const int32_t* pickdesc, hipStream_t s) {
   const int32_t rows = kBlock ? gcap + 1 : gcap;
-  auto plain = momdesc  ? win_combine_kernel<kBlock, true, true, false>
-               : m2desc ? win_combine_kernel<kBlock, true, false, false>
-                        : win_combine_kernel<kBlock, false, false, false>;
-  auto keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true>
-               : m2desc ? win_combine_kernel<kBlock, true, false, true>
-                        : win_combine_kernel<kBlock, false, false, true>;
-  hipLaunchKernelGGL(lodesc ? keyed : plain, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s,
-                     ring, (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap,
-                     kBlock ? rows : 0, out, m2desc, momdesc, lodesc);
+  auto plain = momdesc  ? win_combine_kernel<kBlock, true, true, false, false>
+               : m2desc ? win_combine_kernel<kBlock, true, false, false, false>
+                        : win_combine_kernel<kBlock, false, false, false, false>;
+  auto keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true, false>
+               : m2desc ? win_combine_kernel<kBlock, true, false, true, false>
+                        : win_combine_kernel<kBlock, false, false, true, false>;
+  // with row picks (``pickdesc``): the same choices, with the pick branch
+  auto pick_plain = momdesc  ? win_combine_kernel<kBlock, true, true, false, true>
+                    : m2desc ? win_combine_kernel<kBlock, true, false, false, true>
+                             : win_combine_kernel<kBlock, false, false, false, true>;
+  auto pick_keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true, true>
+                    : m2desc ? win_combine_kernel<kBlock, true, false, true, true>
+                             : win_combine_kernel<kBlock, false, false, true, true>;
+  auto kernel = pickdesc ? (lodesc ? pick_keyed : pick_plain) : (lodesc ? keyed : plain);
+  hipLaunchKernelGGL(kernel, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s, ring,
+                     (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap, kBlock ? rows : 0, out,
+                     m2desc, momdesc, lodesc, pickdesc);
 }
 
 // a block of ring slots pre-combined into another ring slot (every row is written, so groups the dictionary gains
@@ -1081,12 +1247,13 @@ static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t
 DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, const int32_t* slots, int32_t nslots,
                                   const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
                                   const int32_t* m2desc_host, const int32_t* momdesc, const int32_t* momdesc_host,
-                                  const int32_t* lodesc, const int32_t* lodesc_host, void* st) {
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, stride))
+                                  const int32_t* lodesc, const int32_t* lodesc_host, const int32_t* pickdesc,
+                                  const int32_t* pickdesc_host, void* st) {
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, stride))
     return (int)hipErrorInvalidValue;
   unsigned long long* r = (unsigned long long*)ring;
   launch_combine<true>(r, gcap, stride, slots, nslots, line_op, scal, r + (int64_t)dst * (gcap + 1) * stride, m2desc,
-                       momdesc, lodesc, (hipStream_t)st);
+                       momdesc, lodesc, pickdesc, (hipStream_t)st);
   return (int)hipGetLastError();
 }
 
@@ -1099,16 +1266,16 @@ DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const
                            int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
                            const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
                            const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
-                           void* st) {
+                           const int32_t* pickdesc, const int32_t* pickdesc_host, void* st) {
   hipStream_t s = (hipStream_t)st;
   const EmitArgs* ea = (const EmitArgs*)emit;
   const PairFolds* pf = (const PairFolds*)folds;
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, stride) || !folds_ok(pf, stride) ||
-      (ea && (!dictcols || !emit_ok(*ea, stride))))
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, stride) ||
+      !folds_ok(pf, stride) || (ea && (!dictcols || !emit_ok(*ea, stride))))
     return (int)hipErrorInvalidValue;
   hipMemsetAsync(scal + 2, 0, 4, s);
   launch_combine<false>((const unsigned long long*)ring, gcap, stride, slots, nslots, line_op, scal,
-                        (unsigned long long*)acc, m2desc, momdesc, lodesc, s);
+                        (unsigned long long*)acc, m2desc, momdesc, lodesc, pickdesc, s);
   for (int k = 0; pf && k < pf->n; ++k)
     hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf->p[k].pcap + 15) >> 4, 256, 256 * 8)),
                        dim3(256), 0, s, pf->p[k], slots, nslots, scal, gcap, (double*)acc, stride);
@@ -1131,7 +1298,7 @@ DXA_API int dxa_win_live(const void* ring, int32_t gcap, int32_t stride, const i
                          const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
                          int64_t* out_idx, void* st) {
   return dxa_win_answer(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
 }
 
 // The dictionary's key columns into fresh ones (``dst`` is zero-filled; earlier batches' output strings are views of
@@ -1289,5 +1456,35 @@ DXA_API int dxa_win_dec(const void* args, void* st) {
   }
   if (m.n <= 0 || m.nargs == 0) return 0;
   hipLaunchKernelGGL(win_dec_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
+  return (int)hipGetLastError();
+}
+
+// ---- first / last / max_by / min_by: the pane's pick pass -----------------------------------------------------------
+
+DXA_API int dxa_win_pick_size() { return (int)sizeof(PickArgs); }
+
+// a pane's rank words, then its payload and validity words, on the same stream after dxa_aggregate_multi filled the
+// slot's key words (win_pick_kernel, win_pick_gather_kernel)
+DXA_API int dxa_win_pick(const void* args, void* st) {
+  const PickArgs& m = *(const PickArgs*)args;
+  if (m.nrank < 1 || m.nrank > kMaxPickJobs || m.nval < 1 || m.nval > kMaxPickJobs || m.gcap < 0 || m.stride <= 0 ||
+      !m.gid || !m.row || !m.scal)
+    return (int)hipErrorInvalidValue;
+  for (int k = 0; k < m.nrank; ++k) {
+    const PickRank& a = m.rank[k];
+    if (a.r < 0 || a.r >= m.stride || (a.last != 0 && a.last != 1)) return (int)hipErrorInvalidValue;
+    if (a.y && (a.k < 0 || a.k >= m.stride || a.k == a.r || ((a.kind & 3) != 1 && (a.kind & 3) != 3) || (a.kind & ~7)))
+      return (int)hipErrorInvalidValue;
+  }
+  for (int k = 0; k < m.nval; ++k) {
+    const PickVal& a = m.val[k];
+    if (!a.x || a.r < 0 || a.r >= m.stride || a.p < 0 || a.p >= m.stride || a.v < 0 || a.v >= m.stride ||
+        a.p == a.v || a.p == a.r || a.v == a.r || (a.last != 0 && a.last != 1))
+      return (int)hipErrorInvalidValue;
+  }
+  if (m.n <= 0) return 0;
+  hipStream_t s = (hipStream_t)st;
+  hipLaunchKernelGGL(win_pick_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, s, m);
+  hipLaunchKernelGGL(win_pick_gather_kernel, dim3(dxa_blocks(m.gcap, 256, 1024)), dim3(256), 0, s, m);
   return (int)hipGetLastError();
 }

@@ -333,6 +333,11 @@ _F_COVAR_POP, _F_COVAR_SAMP, _F_CORR, _F_SKEW, _F_KURT = 32, 64, 96, 128, 160
 _MA_LOKEY = 5
 _F_DEC_MM, _F_DEC_SUM, _F_DEC_AVG, _F_HI = 7, 192, 224, 16
 _DEC_SUM, _DEC_KEY_MAX, _DEC_KEY_MIN = 0, 1, 2           # win_dec_kernel's job kinds
+# and for row picks (first / last / max_by / min_by): the combine ops of the rank words (identity INT64_MIN) and of
+# the payload / validity words (identity 0), described per word by ``pickdesc``: R word | (K word + 1) << 8 |
+# last << 16 | 1 << 17
+_MA_PICK_RANK, _MA_PICK_VAL = 6, 7
+_PICK_LAST, _PICK_USED = 1 << 16, 1 << 17
 _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096
