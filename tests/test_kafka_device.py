@@ -138,7 +138,9 @@ def test_device_decode_launch_sizing(gpu):
 @pytest.mark.parametrize("level", [1, 6, 9])
 def test_device_inflate_matches_host(gpu, level):
     """gzip record batches inflated on the GPU (inflate.hip) next to LZ4 and uncompressed batches in one fetch: fixed
-    and dynamic Huffman blocks, stored blocks (incompressible values), long matches and RLE runs."""
+    and dynamic Huffman blocks, stored blocks (incompressible values), long matches and RLE runs.  This is the
+    end-to-end path on zlib's output; the format's edges (long codes, far distances, header run-length codes, every
+    malformed-stream class) are in tests/test_codec_vectors.py."""
     import zlib
     rnd = random.Random(level)
     vals = _values(2500, seed=30 + level)

@@ -11,41 +11,7 @@ import torch
 
 from dxa.io import kafka as K
 from dxa.ops import lz4
-
-
-def _py_block_decode(src: bytes) -> bytes:
-    out = bytearray()
-    i = 0
-    while i < len(src):
-        tok = src[i]
-        i += 1
-        lit = tok >> 4
-        if lit == 15:
-            while True:
-                b = src[i]
-                i += 1
-                lit += b
-                if b != 255:
-                    break
-        out += src[i:i + lit]
-        i += lit
-        if i >= len(src):
-            break
-        off = src[i] | (src[i + 1] << 8)
-        i += 2
-        ml = tok & 15
-        if ml == 15:
-            while True:
-                b = src[i]
-                i += 1
-                ml += b
-                if b != 255:
-                    break
-        ml += 4
-        assert 0 < off <= len(out)
-        for _ in range(ml):
-            out.append(out[-off])
-    return bytes(out)
+from tests.codec_vectors import py_lz4_block_decode as _py_block_decode
 
 
 def _py_frame_decode(f: bytes) -> bytes:
@@ -185,7 +151,9 @@ def test_gpu_newline_framing():
 def test_gpu_lz4_wave_decoder_edge_cases():
     """The wave-per-block LDS decoder against the host codec: incompressible literal runs longer than the 512-B
     register window, RLE runs (offset 1), short periods (offset < 64), long matches, odd block sizes (unaligned
-    16-B flush), and > 64 KiB blocks (per-lane fallback)."""
+    16-B flush), and > 64 KiB blocks (per-lane fallback).  These frames come from this project's own encoder; the
+    kernel's window, fast-path and pipeline edges on hand-built and pyarrow blocks, and malformed blocks, are in
+    tests/test_codec_vectors.py."""
     assert torch.cuda.is_available()
     dev = torch.device("cuda", 0)
     rnd = random.Random(11)
