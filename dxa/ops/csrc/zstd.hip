@@ -235,8 +235,7 @@ __device__ bool build_fse(ZTables& T, int nsym, int log, uint32_t* tab) {
   }
   const int step = (size >> 1) + (size >> 3) + 3;
   int pos = 0;
-  if (high < 0) return false;
-  int placed = 0;
+  int placed = 0;                       // (high == -1: every cell went to a "less than one" symbol, which is legal)
   for (int s = 0; s < nsym; ++s) {
     const int cnt = T.norm[s];
     placed += cnt > 0 ? cnt : 0;
@@ -564,7 +563,9 @@ __device__ int32_t decode_block(const uint8_t* in, int32_t n, uint8_t* out, int3
       put_lits(ll);
       op += ll;
       lpos += ll;
-      if (off == 0 || (int32_t)off > op) return Z_OFFSET;
+      // unsigned: an offset of 2^31 or more (offset code 31) must not turn negative and pass.  A rejected offset
+      // stays in fs.rep0, but every error ends the frame, so no later sequence reads it.
+      if (off == 0 || off > (uint32_t)op) return Z_OFFSET;
       const int32_t s = op - (int32_t)off;
       if (s + (ml < (int32_t)off ? ml : (int32_t)off) > done) {   // source reaches past the visible output
         stores_visible();

@@ -1,15 +1,16 @@
-"""Hand-assembled DEFLATE, LZ4-block and snappy-raw-block streams for ``tests/test_codec_vectors.py``.
+"""Hand-assembled DEFLATE, LZ4-block and snappy-raw-block streams and Zstandard frames for
+``tests/test_codec_vectors.py``.
 
 Every stream is built from an explicit symbol list by a writer that follows the format description (RFC 1951, the
-LZ4 block format, the snappy format description), and its expected bytes come from the writer's own plain expansion
-of that list — never from a decoder.  This module runs no tests.
+LZ4 block format, the snappy format description, RFC 8878), and its expected bytes come from the writer's own plain
+expansion of that list — never from a decoder.  This module runs no tests.
 
 A valid vector is ``Vec(name, comp, expected)``.  A malformed one is ``Bad(name, comp, None, klass, cap)``: ``klass``
 names the status class a decoder must report and ``cap`` is the output capacity it is given.  Malformed vectors are
 chosen so that a decoder *without* the relevant check still stays near its slot: it reaches at most one byte before
-the output, overruns it by a few bytes, and over-reads the input by fewer bytes than follow every member.  (The two
-offset-0 vectors are the exception the formats force: what a decoder without that check reads is its own slot, but
-a `x % 0` in its copy loop is not defined.)
+the output, overruns it by a few bytes, and over-reads the input by fewer bytes than follow every member.  (The
+offset-0 vectors, two for LZ4 and snappy and one for zstd, are the exception the formats force: what a decoder
+without that check reads is its own slot, but a `x % 0` in its copy loop is not defined.)
 """
 from __future__ import annotations
 
@@ -29,13 +30,13 @@ class Bad(NamedTuple):
     name: str
     comp: bytes
     expected: Optional[bytes]     # always None
-    klass: str                    # "trunc" | "offset" | "overflow" | "size" | "block" | "code"
+    klass: str                    # "trunc" | "offset" | "overflow" | "size" | "block" | "code" | zstd's "z_..."
     cap: int
     stream_ok: bool = False       # the stream itself is well-formed: only the capacity given with it is wrong
 
 
 def noise(n: int, seed: int) -> bytes:
-    return bytes(random.Random(seed).getrandbits(8) for _ in range(n))
+    return random.Random(seed).randbytes(n)      # (one generator for all n bytes: a new one per byte repeats a byte)
 
 
 # =====================================================================================================================
@@ -777,6 +778,1000 @@ def snappy_vectors():
     bad("output_one_byte_short", snappy_block([("lit", b"0123456789", 0), ("copy1", 10, 6)], preamble=17)[0],
         "size", 17)
     return tuple(V), tuple(B)
+
+
+# =====================================================================================================================
+# Zstandard frames (RFC 8878)
+# =====================================================================================================================
+ZSTD_MAGIC = 0xFD2FB528
+LL_DEF = [4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1,
+          -1]
+OF_DEF = [1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1]
+ML_DEF = [1, 4, 3, 2, 2, 2, 2, 2, 2] + [1] * 37 + [-1] * 7
+ZLL_BASE = list(range(16)) + [16, 18, 20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384,
+                              32768, 65536]
+ZLL_BITS = [0] * 16 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+ZML_BASE = list(range(3, 35)) + [35, 37, 39, 41, 43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051, 4099, 8195,
+                                 16387, 32771, 65539]
+ZML_BITS = [0] * 32 + [1, 1, 1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
+ZBLOCK_MAX = 128 * 1024
+PRE, REP = "pre", "rep"            # sequence-table modes 0 and 3; RLE(sym) is mode 1 and FSE(norm, log) mode 2
+ZSTD_KINDS = ("ll", "of", "ml")
+ZSTD_DEFAULTS = {"ll": (LL_DEF, 6), "of": (OF_DEF, 5), "ml": (ML_DEF, 6)}
+ZSTD_MAX_SYM = {"ll": 35, "of": 31, "ml": 52}
+ZSTD_MAX_LOG = {"ll": 9, "of": 8, "ml": 9}
+
+
+def RLE(sym):
+    return ("rle", sym)
+
+
+def FSE(norm, log, desc=None):
+    """``desc`` replaces the table description written for ``norm`` (a malformed vector's own bytes)."""
+    return ("fse", tuple(norm), log, desc)
+
+
+def fse_table(norm, log):
+    """RFC 8878 4.1.1 decoding table of a normalized distribution: [(symbol, nbits, baseline)] per state."""
+    size = 1 << log
+    sym = [0] * size
+    high = size - 1
+    for s, c in enumerate(norm):
+        if c == -1:
+            sym[high] = s
+            high -= 1
+    step, pos = (size >> 1) + (size >> 3) + 3, 0
+    for s, c in enumerate(norm):
+        for _ in range(max(c, 0)):
+            sym[pos] = s
+            pos = (pos + step) & (size - 1)
+            while pos > high:
+                pos = (pos + step) & (size - 1)
+    nxt = [1 if c == -1 else c for c in norm]
+    cells = []
+    for c in range(size):
+        s = sym[c]
+        x = nxt[s]
+        nxt[s] += 1
+        nb = log - (x.bit_length() - 1)
+        cells.append((s, nb, (x << nb) - size))
+    return cells
+
+
+class BackWriter:
+    """Bits written low to high; the decoder reads them high to low (a zstd backward bitstream)."""
+
+    def __init__(self):
+        self.v, self.n = 0, 0
+
+    def put(self, value, nbits):
+        self.v |= (value & ((1 << nbits) - 1)) << self.n
+        self.n += nbits
+
+    def finish(self):
+        self.put(1, 1)                                    # the end marker
+        nbytes = (self.n + 7) // 8
+        return self.v.to_bytes(nbytes, "little")
+
+
+_XP = (11400714785074694791, 14029467366897019727, 1609587929392839161, 9650029242287828579, 2870177450012600261)
+_M64 = (1 << 64) - 1
+
+
+def xxh64(data: bytes, seed: int = 0) -> int:
+    """XXH64 (the frame's content checksum is its low 32 bits), from the algorithm description."""
+    p1, p2, p3, p4, p5 = _XP
+    rotl = lambda x, r: ((x << r) | (x >> (64 - r))) & _M64                    # noqa: E731
+    rnd = lambda acc, v: (rotl((acc + v * p2) & _M64, 31) * p1) & _M64          # noqa: E731
+    le = lambda i, k: int.from_bytes(data[i:i + k], "little")                  # noqa: E731
+    n, i = len(data), 0
+    if n >= 32:
+        v = [(seed + p1 + p2) & _M64, (seed + p2) & _M64, seed, (seed - p1) & _M64]
+        while i + 32 <= n:
+            for k in range(4):
+                v[k] = rnd(v[k], le(i + 8 * k, 8))
+            i += 32
+        h = (rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) + rotl(v[3], 18)) & _M64
+        for k in range(4):
+            h = ((h ^ rnd(0, v[k])) * p1 + p4) & _M64
+    else:
+        h = (seed + p5) & _M64
+    h = (h + n) & _M64
+    while i + 8 <= n:
+        h = (rotl(h ^ rnd(0, le(i, 8)), 27) * p1 + p4) & _M64
+        i += 8
+    if i + 4 <= n:
+        h = (rotl(h ^ (le(i, 4) * p1) & _M64, 23) * p2 + p3) & _M64
+        i += 4
+    while i < n:
+        h = (rotl(h ^ (data[i] * p5) & _M64, 11) * p1) & _M64
+        i += 1
+    h = ((h ^ (h >> 33)) * p2) & _M64
+    h = ((h ^ (h >> 29)) * p3) & _M64
+    return h ^ (h >> 32)
+
+
+class FseDesc:
+    """Writer of an FSE table description (RFC 8878 4.1.1), one field at a time: ``count`` a normalized count (-1 for
+    "less than one"), ``zeros`` the repeat flags that follow a count of 0 (how many *more* symbols have count 0)."""
+
+    def __init__(self, log, log_field=None):
+        self.bw = BitWriter()
+        self.bw.bits(log - 5 if log_field is None else log_field, 4)
+        self.remaining, self.threshold, self.nbits = (1 << log) + 1, 1 << log, log + 1
+        self.flags = []                                   # the zero-run values written
+
+    def count(self, c):
+        value, mx = c + 1, (2 * self.threshold - 1) - self.remaining
+        assert 0 <= value <= self.remaining, (c, self.remaining)
+        if value < mx:
+            self.bw.bits(value, self.nbits - 1)
+        elif value < self.threshold:
+            self.bw.bits(value, self.nbits)
+        else:
+            self.bw.bits(value + mx, self.nbits)
+        self.remaining -= abs(c)
+        while self.remaining < self.threshold:
+            self.nbits -= 1
+            self.threshold >>= 1
+        return self
+
+    def zeros(self, more):
+        self.flags.append(more)
+        while more >= 3:                                  # sixteen 1-bits in a row are the "24 zeros" form
+            self.bw.bits(3, 2)
+            more -= 3
+        self.bw.bits(more, 2)
+        return self
+
+    def finish(self):
+        return self.bw.getvalue()
+
+
+def fse_description(norm, log, info=None):
+    """The description of ``norm`` (which ends with its last nonzero count); ``info``: a dict that takes the zero-run
+    values written and the number of bits."""
+    assert sum(abs(c) for c in norm) == 1 << log and norm[-1] != 0, (norm, log)
+    d = FseDesc(log)
+    s = 0
+    while s < len(norm):
+        d.count(norm[s])
+        s += 1
+        if norm[s - 1] == 0:
+            more = 0
+            while norm[s + more] == 0:
+                more += 1
+            d.zeros(more)
+            s += more
+    assert d.remaining == 1
+    if info is not None:
+        info.setdefault("zero_runs", []).extend(d.flags)
+        info.setdefault("desc_bits", []).append(d.bw.bitpos)
+    return d.finish()
+
+
+def _state_of(table, symbol, then, rnd, want=None):
+    """A state that decodes ``symbol`` and whose update can reach state ``then`` (for each symbol the cells' ranges
+    [baseline, baseline + 2^nbits) tile the whole table, so one exists); any cell of the symbol if ``then`` is None."""
+    cells = [i for i, c in enumerate(table) if c[0] == symbol and (then is None or c[2] <= then < c[2] + (1 << c[1]))]
+    assert cells, ("no state", symbol, then)
+    if want is not None:
+        cells = [i for i in cells if want(table[i])] or cells
+    return rnd.choice(cells)
+
+
+def flat_norm(symbols, log):
+    """A distribution over 0..max(symbols): 1 for every symbol present, the rest of 2^log to the commonest."""
+    norm = [0] * (max(symbols) + 1)
+    for s in set(symbols):
+        norm[s] = 1
+    top = max(set(symbols), key=lambda s: (symbols.count(s), -s))
+    norm[top] += (1 << log) - sum(norm)
+    assert norm[top] >= 1
+    return norm
+
+
+def huf_codes(weights):
+    """{symbol: (code, nbits)} of a complete weight list (the last symbol's implied weight included), and the tree's
+    depth: symbols of weight w take 2^(w-1) consecutive table cells, weights ascending, then symbol order."""
+    total = sum(1 << (w - 1) for w in weights if w)
+    maxb = total.bit_length() - 1
+    assert total == 1 << maxb and 1 <= maxb <= 11 and weights[-1], (total, weights)
+    codes, start = {}, 0
+    for k in range(1, maxb + 1):
+        for s, w in enumerate(weights):
+            if w == k:
+                codes[s] = (start >> (k - 1), maxb + 1 - k)
+                start += 1 << (k - 1)
+    return codes, maxb
+
+
+def huf_stream(data, codes):
+    w = BackWriter()
+    for b in reversed(data):
+        w.put(*codes[b])
+    return w.finish(), w.n - 1
+
+
+def huf_tree_direct(listed):
+    assert 1 <= len(listed) <= 128
+    ws = list(listed) + [0]
+    return bytes([127 + len(listed)]) + bytes((ws[i] << 4) | ws[i + 1] for i in range(0, len(listed), 2))
+
+
+def huf_tree_fse(listed, log, norm=None, log_field=None, rnd=None):
+    """FSE-compressed weights: a table description, then one backward bitstream that two states read in turn.  The
+    decoder stops when an update reads past the start of the stream: the stream ends exactly before the update that
+    follows the last weight but one, which is taken from a cell that reads at least one bit."""
+    rnd = rnd or random.Random(len(listed))
+    n = len(listed)
+    assert n >= 2
+    norm = norm or flat_norm(list(listed), log)
+    tab = fse_table(norm, log)
+    st = [None] * n
+    st[n - 1] = _state_of(tab, listed[n - 1], None, rnd)
+    st[n - 2] = _state_of(tab, listed[n - 2], None, rnd, want=lambda c: c[1] >= 1)
+    assert tab[st[n - 2]][1] >= 1
+    for i in range(n - 3, -1, -1):
+        st[i] = _state_of(tab, listed[i], st[i + 2], rnd)
+    w = BackWriter()
+    for i in range(n - 3, -1, -1):
+        c = tab[st[i]]
+        w.put(st[i + 2] - c[2], c[1])
+    w.put(st[1], log)
+    w.put(st[0], log)
+    desc = fse_description(norm, log)
+    if log_field is not None:
+        desc = bytes([(desc[0] & 0xF0) | log_field]) + desc[1:]
+    body = desc + w.finish()
+    assert len(body) < 128, len(body)
+    return bytes([len(body)]) + body
+
+
+def zcode(value, base, bits):
+    i = max(k for k in range(len(base)) if base[k] <= value)
+    assert value - base[i] < (1 << bits[i]), value
+    return i, value - base[i]
+
+
+def OFF(offset):
+    """Offset value of a real offset (values 1..3 are the repeat codes)."""
+    return offset + 3
+
+
+class ZFrame:
+    """One frame: block writers that emit the bytes and expand the same description into ``out``.
+
+    Literals: ("raw", data, header bytes 1..3) | ("rle", byte, count, header bytes)
+    | ("huf", data, weights, streams, size format, "direct" | ("fse", log[, norm])) | ("treeless", data, streams,
+    size format).  Sequences: (literal length, offset value, match length)."""
+
+    def __init__(self, window=(10, 0), fcs=None, checksum=False, did=0, seed=1):
+        self.window, self.fcs, self.checksum, self.did = window, fcs, checksum, did
+        self.blocks = []
+        self.out = bytearray()
+        self.rep = [1, 4, 8]
+        self.tabs = {}                   # kind -> (cells, log) of the last table
+        self.huf = None                  # (codes, depth) of the last tree
+        self.rnd = random.Random(seed)
+        self.broken = False              # a sequence had no valid expansion (malformed vectors)
+        self.info = {"cell_bits": set(), "marker_bit": [], "seq_bytes": [], "seq_bits": [], "rep_idx": set(),
+                     "huf_stream_bytes": [], "huf_depth": []}
+
+    # ---- blocks
+    def _block(self, typ, size, payload):
+        self.blocks.append((typ, size, bytes(payload)))
+        return self
+
+    def raw(self, data):
+        self.out += data
+        return self._block(0, len(data), data)
+
+    def rle(self, byte, count):
+        self.out += bytes([byte]) * count
+        return self._block(1, count, bytes([byte]))
+
+    def compressed(self, lits, seqs, ll=PRE, of=PRE, ml=PRE, size=None, **kw):
+        sec, data = self._literals(lits)
+        body = sec + self._sequences(seqs, data, {"ll": ll, "of": of, "ml": ml}, **kw)
+        return self._block(2, len(body) if size is None else size, body)
+
+    # ---- literals
+    @staticmethod
+    def _lit_header(lt, regen, hdr):
+        if hdr == 1:                                      # (size format ?0: bit 3 is the size's lowest bit)
+            assert regen < 32
+            return bytes([lt | (regen << 3)])
+        assert regen < (1 << (12 if hdr == 2 else 20))
+        return (lt | ((1 if hdr == 2 else 3) << 2) | (regen << 4)).to_bytes(hdr, "little")
+
+    def _literals(self, lits):
+        kind = lits[0]
+        if kind == "raw":
+            data = lits[1]
+            return self._lit_header(0, len(data), *lits[2:]) + data, data
+        if kind == "rle":
+            return self._lit_header(1, lits[2], *lits[3:]) + bytes([lits[1]]), bytes([lits[1]]) * lits[2]
+        tree = b""
+        if kind == "huf":
+            _, data, weights, streams, sf, how = lits[:6]
+            self.huf = huf_codes(weights)
+            listed = weights[:-1]
+            tree = huf_tree_direct(listed) if how == "direct" else huf_tree_fse(listed, *how[1:], rnd=self.rnd)
+            opts = lits[6] if len(lits) > 6 else {}
+        else:
+            _, data, streams, sf = lits[:4]
+            opts = lits[4] if len(lits) > 4 else {}
+        tree = opts.get("tree", tree)
+        assert (streams, sf) in ((1, 0), (4, 1), (4, 2), (4, 3))
+        body = b""
+        if self.huf is not None:
+            codes = self.huf[0]
+            self.info["huf_depth"].append(self.huf[1])
+            if streams == 1:
+                body, _ = huf_stream(data, codes)
+                self.info["huf_stream_bytes"].append(len(body))
+            else:
+                per = (len(data) + 3) // 4
+                parts = [huf_stream(data[k * per:(k + 1) * per if k < 3 else len(data)], codes)[0] for k in range(4)]
+                self.info["huf_stream_bytes"] += [len(p) for p in parts]
+                jump = opts.get("jump", [len(p) for p in parts[:3]])
+                body = b"".join(j.to_bytes(2, "little") for j in jump) + b"".join(parts)
+        body = opts.get("body", lambda b: b)(body)
+        regen = len(data) + opts.get("regen_delta", 0)
+        csize = len(tree) + len(body) + opts.get("csize_delta", 0)
+        lt = 2 if kind == "huf" else 3
+        width, nbytes = ((10, 3), (10, 3), (14, 4), (18, 5))[sf]
+        assert regen < (1 << width) and csize < (1 << width), (regen, csize, sf)
+        hdr = (lt | (sf << 2) | (regen << 4) | (csize << (4 + width))).to_bytes(nbytes, "little")
+        return hdr + tree + body, data
+
+    # ---- sequences
+    def _table(self, kind, mode):
+        """(mode number, bytes written for it); sets self.tabs[kind]."""
+        if mode == PRE:
+            norm, log = ZSTD_DEFAULTS[kind]
+            self.tabs[kind] = (fse_table(norm, log), log)
+            return 0, b""
+        if mode == REP:
+            return 3, b""
+        if mode[0] == "rle":
+            self.tabs[kind] = ([(mode[1], 0, 0)], 0)
+            return 1, bytes([mode[1]])
+        _, norm, log, desc = mode
+        self.tabs[kind] = (fse_table(norm, log), log)
+        return 2, fse_description(norm, log, self.info) if desc is None else desc
+
+    def _expand(self, seqs, data):
+        out, rep, lp = self.out, self.rep, 0
+        for L, ofv, M in seqs:
+            if self.broken or L > len(data) - lp:
+                self.broken = True
+                return
+            out += data[lp:lp + L]
+            lp += L
+            if ofv > 3:
+                off = ofv - 3
+                rep[:] = [off, rep[0], rep[1]]
+            else:
+                idx = ofv - 1 + (L == 0)
+                self.info["rep_idx"].add(idx)
+                off = rep[0] - 1 if idx == 3 else rep[idx]
+                if idx == 1:
+                    rep[:] = [off, rep[0], rep[2]]
+                elif idx >= 2:
+                    rep[:] = [off, rep[0], rep[1]]
+            if not 1 <= off <= len(out):
+                self.broken = True
+                return
+            if off >= M:
+                out += out[len(out) - off:len(out) - off + M]
+            else:
+                for _ in range(M):
+                    out.append(out[-off])
+        out += data[lp:]
+
+    def _sequences(self, seqs, data, modes, count_bytes=None, reserved=0, pad_low=0, drop_low=0, tail=None):
+        n = len(seqs)
+        self._expand(seqs, data)
+        if count_bytes is None:
+            count_bytes = 1 if n < 128 else 2 if n < 0x7F00 else 3
+        if count_bytes == 1:
+            assert n < 128
+            head = bytes([n])
+        elif count_bytes == 2:
+            assert n < 0x7F00
+            head = bytes([128 + (n >> 8), n & 255])
+        else:
+            assert 0x7F00 <= n < 0x7F00 + 65536
+            head = b"\xff" + (n - 0x7F00).to_bytes(2, "little")
+        if n == 0:
+            return head
+        mb, descs = reserved, b""
+        for k, kind in enumerate(ZSTD_KINDS):
+            m, d = self._table(kind, modes[kind])
+            mb |= m << (6 - 2 * k)
+            descs += d
+        head += bytes([mb]) + descs
+        if tail is not None:                              # a malformed vector's own bitstream
+            return head + tail
+        tabs = [self.tabs[k][0] for k in ZSTD_KINDS]
+        logs = [self.tabs[k][1] for k in ZSTD_KINDS]
+        code = []
+        for L, ofv, M in seqs:
+            oc = ofv.bit_length() - 1
+            lc, mc = zcode(L, ZLL_BASE, ZLL_BITS), zcode(M, ZML_BASE, ZML_BITS)
+            code.append((lc + (ZLL_BITS[lc[0]],), (oc, ofv - (1 << oc), oc), mc + (ZML_BITS[mc[0]],)))
+        # For each symbol the cells' ranges tile the table, so the state of the last sequence fixes every earlier
+        # one.  Of the chains that end in each cell of the last symbol, take the one whose updates read the most
+        # different bit counts (0 bits and `log` bits first).
+        chains = []
+        for k in range(3):
+            cover = {}
+            for idx, c in enumerate(tabs[k]):
+                for t in range(c[2], c[2] + (1 << c[1])):
+                    cover[(c[0], t)] = idx
+            best = None
+            for last in (idx for idx, c in enumerate(tabs[k]) if c[0] == code[n - 1][k][0]):
+                chain = [last]
+                for i in range(n - 2, -1, -1):
+                    chain.append(cover[(code[i][k][0], chain[-1])])
+                chain.reverse()
+                read = {tabs[k][x][1] for x in chain[:-1]}
+                score = (len(read & {0, logs[k]}), len(read), self.rnd.random())
+                if best is None or score > best[0]:
+                    best = (score, chain)
+                if n > 1000:
+                    break
+            assert best is not None, ("no state decodes", ZSTD_KINDS[k], code[n - 1][k][0])
+            chains.append(best[1])
+        st = list(zip(*chains))
+        w = BackWriter()
+        w.put(0, pad_low)
+        for i in range(n - 1, -1, -1):
+            if i + 1 < n:                                 # state updates are read LL, ML, OF
+                for k in (1, 2, 0):
+                    c = tabs[k][st[i][k]]
+                    w.put(st[i + 1][k] - c[2], c[1])
+                    self.info["cell_bits"].add((ZSTD_KINDS[k], logs[k], c[1]))
+            for k in (0, 2, 1):                           # extra bits are read OF, ML, LL
+                w.put(code[i][k][1], code[i][k][2])
+        for k in (2, 1, 0):                               # initial states are read LL, OF, ML
+            w.put(st[0][k], logs[k])
+        if drop_low:
+            w.v >>= drop_low
+            w.n -= drop_low
+        self.info["marker_bit"].append(w.n % 8)
+        self.info["seq_bits"].append(w.n)
+        bits = w.finish()
+        self.info["seq_bytes"].append(len(bits))
+        return head + bits
+
+    # ---- frame
+    def finish(self, magic=ZSTD_MAGIC, fhd_or=0, did_value=0, fcs_delta=0, no_last=False, fcs_value=None):
+        single = self.window is None
+        fcs = self.fcs if self.fcs is not None else (1 if single else 0)
+        assert fcs in (0, 1, 2, 4, 8) and (fcs != 1 or single) and (fcs != 0 or not single)
+        n = (len(self.out) if fcs_value is None else fcs_value) + fcs_delta
+        fhd = ({0: 0, 1: 0, 2: 1, 4: 2, 8: 3}[fcs] << 6) | (single << 5) | (self.checksum << 2) | \
+            {0: 0, 1: 1, 2: 2, 4: 3}[self.did] | fhd_or
+        f = bytearray(magic.to_bytes(4, "little") + bytes([fhd]))
+        if not single:
+            f.append((self.window[0] << 3) | self.window[1])
+        f += did_value.to_bytes(self.did, "little")
+        if fcs:
+            f += (n - 256 if fcs == 2 else n).to_bytes(fcs, "little")
+        self.header_len = len(f)
+        for i, (typ, size, payload) in enumerate(self.blocks):
+            last = i + 1 == len(self.blocks) and not no_last
+            f += (int(last) | (typ << 1) | (size << 3)).to_bytes(3, "little") + payload
+        if self.checksum:
+            f += (xxh64(bytes(self.out)) & 0xFFFFFFFF).to_bytes(4, "little")
+        return bytes(f), bytes(self.out)
+
+
+def huf_chain(depth, syms):
+    """Weights of a tree whose code lengths are 1, 2, .., depth, depth over ``syms`` (in that order)."""
+    assert len(syms) == depth + 1 and len(set(syms)) == len(syms)
+    w = [0] * (max(syms) + 1)
+    for k, s in enumerate(syms):
+        w[s] = max(depth - k, 1)
+    return w
+
+
+def huf_data(weights, n, seed):
+    """n bytes over the symbols of ``weights`` (commoner for heavier ones), every symbol at least once."""
+    syms = [s for s, w in enumerate(weights) if w]
+    rnd = random.Random(seed)
+    body = rnd.choices(syms, weights=[1 << weights[s] for s in syms], k=max(n - len(syms), 0)) + syms
+    rnd.shuffle(body)
+    return bytes(body[:n]) if n < len(syms) else bytes(body)
+
+
+def znorm(log, counts, fill):
+    """Normalized counts from {symbol: count}; ``fill`` takes what is left of 2^log."""
+    norm = [0] * (max(list(counts) + [fill]) + 1)
+    for s, c in counts.items():
+        norm[s] = c
+    norm[fill] += (1 << log) - sum(abs(c) for c in norm)
+    assert norm[fill] >= 1 and norm[-1] != 0, norm
+    return norm
+
+
+def runs_norm(pairs):
+    """Normalized counts from [(count, zero counts that follow it)]."""
+    norm = []
+    for c, z in pairs:
+        norm += [c] + [0] * z
+    return norm
+
+
+def rle_history(f, total, seed, first=509):
+    """``total`` bytes of history as RLE blocks of 509 bytes (4 bytes of frame each) with unrelated values: a match of
+    more than 509 bytes always crosses a boundary, so a wrong offset shows."""
+    rnd = random.Random(seed)
+    left, size, prev = total, first, -1
+    while left:
+        n = min(size, left)
+        v = rnd.choice([x for x in range(256) if x != prev])
+        f.rle(v, n)
+        prev, left, size = v, left - n, 509
+    return f
+
+
+ZH = noise(1100, 900)              # a raw first block: history for offsets up to 1100
+
+
+@functools.lru_cache(maxsize=None)
+def zstd_vectors():
+    """(valid, malformed, coverage) Zstandard frames; ``coverage`` collects what the writers actually emitted."""
+    V, B = [], []
+    cov = {"cell_bits": set(), "marker_bit": set(), "seq_bytes": set(), "rep_idx": set(), "zero_runs": set(),
+           "desc_bits": set(), "huf_stream_bytes": set(), "huf_depth": set()}
+
+    def add(name, f, **kw):
+        comp, out = f.finish(**kw)
+        assert not f.broken, name
+        assert len(out) <= 1 << 20, (name, len(out))
+        V.append(Vec(name, comp, out))
+        for k, v in f.info.items():
+            if k in cov:
+                cov[k] |= set(v)
+        return f
+
+    def bad(name, f, klass, cap, stream_ok=False, cut=None, **kw):
+        comp = f if isinstance(f, bytes) else f.finish(**kw)[0]
+        B.append(Bad(name, comp if cut is None else comp[:cut], None, klass, cap, stream_ok))
+
+    h8, h16, h70 = ZH[:8], ZH[:16], ZH[:70]
+    text = b"{\"deviceId\":17,\"temperature\":21.5,\"status\":\"ok\"}\n" * 4
+    few = [(4, OFF(3), 5), (0, 1, 3), (2, 2, 40), (7, OFF(30), 9)]
+
+    # ------------------------------------------------------------------------------------------------- frame
+    add("fcs_1_byte_single_segment", ZFrame(window=None, fcs=1).raw(noise(100, 901)))
+    add("fcs_2_bytes_at_256", ZFrame(fcs=2).raw(noise(256, 902)))
+    add("fcs_2_bytes_at_65791_single_segment", ZFrame(window=None, fcs=2).raw(noise(65791, 903)))
+    add("fcs_4_bytes", ZFrame(fcs=4).raw(h70).compressed(("raw", text[:31], 1), few))
+    add("fcs_4_bytes_single_segment", ZFrame(window=None, fcs=4).raw(ZH).compressed(("raw", text[:31], 1), few))
+    add("fcs_8_bytes", ZFrame(fcs=8).raw(h70).compressed(("raw", text[:31], 1), few))
+    add("fcs_8_bytes_single_segment", ZFrame(window=None, fcs=8).raw(ZH).compressed(("raw", text[:31], 1), few))
+    add("no_fcs_window_descriptor", ZFrame().raw(h70).compressed(("raw", text[:31], 1), few))
+    add("window_descriptor_1_kib", ZFrame(window=(0, 0)).raw(h70).compressed(("raw", text[:31], 1), few))
+    add("window_descriptor_mantissa_7", ZFrame(window=(3, 7), fcs=2).raw(ZH).compressed(("raw", text[:31], 1), few))
+    add("checksum", ZFrame(checksum=True).raw(ZH).compressed(("raw", text[:31], 1), few).rle(0x33, 77))
+    add("checksum_single_segment_fcs", ZFrame(window=None, fcs=4, checksum=True).raw(ZH).rle(9, 1))
+    add("dictionary_id_0_in_1_byte", ZFrame(did=1).raw(h70))
+    add("dictionary_id_0_in_2_bytes", ZFrame(did=2, fcs=4).raw(h70))
+    add("dictionary_id_0_in_4_bytes", ZFrame(did=4, window=None, fcs=1).raw(h70))
+    add("empty_frame_single_segment", ZFrame(window=None, fcs=1).raw(b""))
+    add("empty_frame_window_descriptor", ZFrame().raw(b""))
+    add("empty_frame_checksum", ZFrame(checksum=True).raw(b""))
+    add("empty_frame_rle_block_of_0", ZFrame().rle(0x77, 0))
+    add("one_raw_block", ZFrame().raw(noise(333, 904)))
+    add("one_raw_block_of_1", ZFrame().raw(b"\x5a"))
+    add("one_rle_block", ZFrame().rle(0x41, 333))
+    add("one_rle_block_of_1", ZFrame().rle(0x41, 1))
+    add("one_rle_block_of_block_maximum", ZFrame().rle(0x42, ZBLOCK_MAX))
+    add("one_raw_block_of_block_maximum", ZFrame().raw(noise(ZBLOCK_MAX, 905)))
+    f = ZFrame(fcs=2)
+    for k in range(3):
+        f.raw(noise(40 + k, 906 + k)).compressed(("raw", text[k:k + 20], 1), [(5, OFF(9 + k), 12), (3, 1, 4)])
+        f.rle(0x61 + k, 19 * k).compressed(("rle", 0x2A, 6, 1), [(2, OFF(50), 33)], ml=RLE(30))
+    add("raw_rle_compressed_interleaved", f)
+
+    # ---------------------------------------------------------------------------------------------- literals
+    for kind in ("raw", "rle"):
+        for hdr, sizes in ((1, (0, 31)), (2, (0, 31, 32, 4095)), (3, (0, 31, 32, 4095, 4096))):
+            for size in sizes:
+                lits = ("raw", noise(size, 910 + size), hdr) if kind == "raw" else ("rle", 0x6B, size, hdr)
+                add(f"literals_{kind}_{size}_header_{hdr}",
+                    ZFrame().raw(h16).compressed(lits, [(min(size, 5), OFF(9), 4)]))
+    w4 = huf_chain(3, [0x65, 0x20, 0x74, 0x61])
+    add("huffman_1_stream", ZFrame().compressed(("huf", huf_data(w4, 300, 1), w4, 1, 0, "direct"), []))
+    add("huffman_1_stream_1_literal", ZFrame().compressed(("huf", b"\x65", w4, 1, 0, "direct"), []))
+    add("huffman_1_stream_1023", ZFrame().compressed(("huf", huf_data(w4, 1023, 2), w4, 1, 0, "direct"), []))
+    for regen, sf in ((8, 1), (1023, 1), (1023, 2), (1024, 2), (16383, 2), (16383, 3), (16384, 3), (300, 3), (300, 2)):
+        add(f"huffman_4_streams_{regen}_format_{sf}",
+            ZFrame().raw(h8).compressed(("huf", huf_data(w4, regen, regen + sf), w4, 4, sf, "direct"),
+                                        [(regen // 2, OFF(5), 6)]))
+    w1 = [0] * 0x30 + [1, 1]
+    for per, last, what in ((40, 40, "shorter_than_8"), (60, 60, "of_8"), (100, 100, "longer_than_8"),
+                            (60, 57, "regen_not_multiple_of_4"), (2, 1, "of_1_byte_regen_7")):
+        d = huf_data(w1, 3 * per + last, per + last)
+        f = add(f"huffman_4_streams_{what}_bytes", ZFrame().compressed(("huf", d, w1, 4, 1, "direct"), []))
+        want = {"shorter_than_8": {6}, "of_8": {8}, "longer_than_8": {13}, "regen_not_multiple_of_4": {8},
+                "of_1_byte_regen_7": {1}}[what]
+        assert set(f.info["huf_stream_bytes"]) == want, (what, f.info["huf_stream_bytes"])
+
+    # ----------------------------------------------------------------------------------------- Huffman trees
+    order = [0x41, 0x7A, 0x30, 0x0A, 0x55, 0xC3, 0x01, 0x99, 0x61, 0xFE, 0x10, 0x80]
+    for depth in range(1, 12):
+        w = huf_chain(depth, order[:depth + 1])
+        how = "direct" if max(order[:depth + 1]) <= 128 else ("fse", 6 if depth % 2 else 5)
+        streams, sf = ((1, 0), (4, 1))[depth % 2]
+        add(f"huffman_depth_{depth}", ZFrame().raw(h8).compressed(
+            ("huf", huf_data(w, 260 + depth, depth), w, streams, sf, how), [(100, OFF(3), 4)]))
+    for nlisted, w in ((1, [1, 1]), (2, [2, 1, 1]), (127, [1] * 128), (128, [2] + [1] * 126 + [0, 8])):
+        assert len(w) == nlisted + 1
+        add(f"huffman_direct_{nlisted}_weights",
+            ZFrame().compressed(("huf", huf_data(w, 400, nlisted), w, 4, 1, "direct"), []))
+    for last_sym in (0x34, 0x35):                          # 52 and 53 weights listed: the loop ends on either state
+        w = huf_chain(3, [0x30, 0x31, 0x33, last_sym])
+        for log in (5, 6):
+            add(f"huffman_fse_{last_sym}_weights_accuracy_{log}",
+                ZFrame().compressed(("huf", huf_data(w, 200, last_sym), w, 1, 0, ("fse", log)), []))
+    w = [1] * 256
+    for log in (5, 6):
+        add(f"huffman_fse_255_weights_accuracy_{log}",
+            ZFrame().compressed(("huf", noise(500, 920 + log), w, 4, 1, ("fse", log, [1, (1 << log) - 1])), []))
+    w = [0] * 200 + [4, 4, 4, 3, 2, 1] + [0] * 49 + [1]          # symbol 255 takes the implied weight
+    add("huffman_fse_mixed_weights_symbol_255", ZFrame().compressed(
+        ("huf", huf_data(w, 700, 5), w, 4, 1, ("fse", 6)), []))
+    d = huf_data(w4, 120, 7)
+    f = ZFrame().raw(h8).compressed(("huf", d, w4, 1, 0, "direct"), few)
+    f.compressed(("treeless", d[:50], 1, 0), [(10, OFF(70), 5)])
+    f.compressed(("raw", text[:20], 1), [(3, 1, 3)]).compressed(("treeless", d[10:110], 4, 1), [(50, 2, 9)])
+    f.raw(b"between").rle(0x21, 13).compressed(("treeless", d[60:90], 4, 2), [])
+    f.compressed(("rle", 0x7E, 9, 1), []).raw(b"").compressed(("treeless", d[:7], 4, 3), [(7, OFF(1), 30)])
+    add("treeless_literals_across_compressed_raw_rle_blocks", f)
+
+    # -------------------------------------------------------------------------------------- FSE descriptions
+    def seqs_with(rnd, llc, ofc, mlc, n):
+        """n sequences that use every given code (extras random; offsets stay inside ZH).  The last three use the
+        first code of each list: a symbol with more than half of the table has its cells of 0 bits where the state
+        value is smallest, and only a run of that symbol at the end of the block is free to pass through them."""
+        out = []
+        for i in range(n):
+            j = 0 if i >= n - 3 else i
+            a, b, c = llc[j % len(llc)], ofc[j % len(ofc)], mlc[j % len(mlc)]
+            assert ZLL_BITS[a] <= 8 and b <= 9 and ZML_BITS[c] <= 8
+            ofv = (1 << b) + rnd.getrandbits(b)
+            if b < 2 and a == 0 and ofv == 3:
+                ofv = 2                                    # (rep0 - 1 needs a known rep0: the repeat-offset vectors)
+            out.append((ZLL_BASE[a] + rnd.getrandbits(ZLL_BITS[a]), ofv, ZML_BASE[c] + rnd.getrandbits(ZML_BITS[c])))
+        return out
+
+    def fse_frame(seed, ll, of, ml, n=48, **kw):
+        rnd = random.Random(seed)
+        tabs = {}
+        for kind, mode in (("ll", ll), ("of", of), ("ml", ml)):
+            norm = ZSTD_DEFAULTS[kind][0] if mode == PRE else mode[1]
+            tabs[kind] = [s for s, c in enumerate(norm) if c and (kind != "ll" or ZLL_BITS[s] <= 8) and
+                          (kind != "of" or s <= 9) and (kind != "ml" or ZML_BITS[s] <= 8)]
+        seqs = seqs_with(rnd, tabs["ll"], tabs["of"], tabs["ml"], n)
+        lits = noise(sum(s[0] for s in seqs) + 5, seed)
+        return ZFrame(seed=seed).raw(ZH).compressed(("raw", lits, 3), seqs, ll=ll, of=of, ml=ml, **kw)
+
+    for log in range(5, 10):
+        half = (1 << (log - 1)) + 3                        # more than half the table: cells that read 0 bits
+        lln = znorm(log, {0: half, 3: -1, 7: 2, 16: 1, 24: -1, 27: 1}, 1)
+        mln = znorm(log, {0: half, 1: -1, 5: 1, 33: 2, 40: -1, 43: 1}, 2)
+        add(f"fse_ll_accuracy_{log}", fse_frame(930 + log, FSE(lln, log), PRE, PRE))
+        add(f"fse_ml_accuracy_{log}", fse_frame(940 + log, PRE, PRE, FSE(mln, log)))
+        if log <= 8:
+            ofn = znorm(log, {0: half, 2: 1, 3: -1, 5: 2, 9: -1}, 1)
+            add(f"fse_of_accuracy_{log}", fse_frame(950 + log, PRE, FSE(ofn, log), PRE))
+            add(f"fse_all_accuracy_{log}", fse_frame(960 + log, FSE(lln, log), FSE(ofn, log), FSE(mln, log), n=60))
+    for kind in ZSTD_KINDS:                                # states with log bits and with 0 bits were both used
+        for log in range(5, ZSTD_MAX_LOG[kind] + 1):
+            assert {(kind, log, log), (kind, log, 0)} <= cov["cell_bits"], (kind, log)
+    # zero runs of 0, 1, 2, 3, 4 and 30 more symbols (the last has the 16-bit form and ends at the last symbol, 52)
+    mln = runs_norm([(20, 1), (5, 2), (5, 3), (5, 4), (3, 5), (7, 31), (19, 0)])
+    assert len(mln) == 53
+    add("fse_ml_every_zero_run_form", fse_frame(970, PRE, PRE, FSE(mln, 6)))
+    lln = runs_norm([(9, 1), (-1, 0), (9, 4), (6, 25), (-1, 0), (6, 0)])   # 24 more: the 16-bit form and flag 0
+    assert len(lln) == 36
+    add("fse_ll_zero_run_of_24_more", fse_frame(971, FSE(lln, 5), PRE, PRE))
+    ofn = runs_norm([(10, 4), (10, 1), (11, 23), (-1, 0)])
+    assert len(ofn) == 32
+    add("fse_of_zero_run_reaches_symbol_31", fse_frame(972, PRE, FSE(ofn, 5), PRE))
+    assert cov["zero_runs"] >= {0, 1, 2, 3, 4, 22, 24, 30}, cov["zero_runs"]
+    assert {b % 8 for b in cov["desc_bits"]} >= {0, 1, 3, 5}, cov["desc_bits"]       # ends mid-byte and on a byte
+    add("fse_ll_highest_symbol_35_used", ZFrame().raw(h16).compressed(
+        ("raw", noise(65540, 973), 3), [(65536 + 3, OFF(11), 4), (0, 1, 3)], ll=FSE(znorm(5, {0: 16}, 35), 5)))
+    add("fse_ml_highest_symbol_52_used", ZFrame().raw(h16).compressed(
+        ("raw", b"ab", 1), [(1, OFF(11), 65539 + 77), (1, 1, 3)], ml=FSE(znorm(5, {0: 16}, 52), 5)))
+    # every cell belongs to a "less than one" symbol: libzstd accepts it (all cells read `log` bits)
+    add("fse_ll_every_cell_less_than_one", fse_frame(974, FSE([-1] * 32, 5), PRE, PRE))
+    add("fse_of_every_cell_less_than_one", fse_frame(975, PRE, FSE([-1] * 32, 5), PRE))
+    add("fse_ml_every_cell_less_than_one", fse_frame(976, PRE, PRE, FSE([0] * 3 + [-1] * 32, 5)))
+
+    # ------------------------------------------------------------------------------------------------- modes
+    lln, ofn, mln = znorm(5, {0: 8, 2: 8, 5: -1}, 1), znorm(5, {1: 4, 4: 8, 6: -1}, 3), znorm(6, {0: 9, 1: 3, 9: -1}, 4)
+    a = [(2, OFF(5), 7), (1, OFF(13), 3), (5, OFF(61), 12), (0, 2, 4)]
+    f = ZFrame().raw(h70)
+    f.compressed(("raw", text[:30], 1), a)                                              # predefined
+    f.compressed(("raw", text[:30], 1), a, ll=REP, of=REP, ml=REP)                      # repeat after predefined
+    r = [(3, OFF(6), 8)] * 3
+    f.compressed(("raw", text[:9], 1), r, ll=RLE(3), of=RLE(3), ml=RLE(5))              # RLE
+    f.compressed(("raw", text[:12], 1), r, ll=REP, of=REP, ml=REP)                      # repeat after RLE
+    f.compressed(("raw", text[:30], 1), a, ll=FSE(lln, 5), of=FSE(ofn, 5), ml=FSE(mln, 6))
+    f.compressed(("raw", text[:11], 1), [])                                             # no sequences: tables stay
+    f.raw(b"raw").rle(0x0D, 5)
+    f.compressed(("raw", text[:30], 1), a, ll=REP, of=REP, ml=REP)                      # repeat after FSE
+    f.compressed(("raw", text[:30], 1), [(2, OFF(5), 7), (1, OFF(13), 7)], ll=PRE, of=REP, ml=RLE(4))
+    f.compressed(("raw", text[:30], 1), [(2, OFF(9), 7)] * 2, ll=RLE(2), of=PRE, ml=REP)
+    f.compressed(("raw", text[:30], 1), [(2, OFF(13), 7), (1, OFF(14), 3), (5, OFF(28), 12)], ll=FSE(lln, 5), of=RLE(4),
+                 ml=PRE)
+    f.compressed(("raw", text[:30], 1), [(5, OFF(15), 12)] * 3, ll=REP, of=REP, ml=FSE(mln, 6))
+    add("every_mode_and_repeat_after_each", f)
+
+    # ------------------------------------------------------------------------------------------------- codes
+    for c in range(36):
+        for ex in sorted({0, (1 << ZLL_BITS[c]) - 1}):
+            n = min(ZLL_BASE[c] + ex, ZBLOCK_MAX - 16)
+            lits = ("raw", noise(n + 2, 1000 + c), 1 if n + 2 < 32 else 2 if n + 2 < 4096 else 3)
+            add(f"ll_code_{c}_length_{n}", ZFrame(seed=c).raw(h16).compressed(lits, [(n, OFF(7 + c), 3)]))
+    for c in range(53):
+        for ex in sorted({0, (1 << ZML_BITS[c]) - 1}):
+            n = min(ZML_BASE[c] + ex, ZBLOCK_MAX - 2)
+            add(f"ml_code_{c}_length_{n}", ZFrame(seed=c).raw(h16).compressed(("raw", b"xy", 1), [(2, OFF(5), n)]))
+    f = rle_history(ZFrame(window=(11, 0)), 525000, 1100)
+    seqs = [(1, 1, 520), (1, 2, 521), (1, 3, 522)]         # offset codes 0 and 1: the initial repeat offsets
+    for c in range(2, 20):
+        seqs += [(1, 1 << c, 520 + c)] + ([(1, (2 << c) - 1, 600 + c)] if c < 19 else [])
+    add("offset_codes_0_to_19", f.compressed(("raw", noise(len(seqs), 1101), 2), seqs))
+    f = rle_history(ZFrame(window=(11, 0)), (1 << 20) - 4, 1102, first=2)
+    add("offset_code_19_extra_all_ones", f.compressed(("raw", b"", 1), [(0, (1 << 20) - 1, 3)]))
+    # one sequence of 17 + 16 + 15 extra bits and 9 + 9 + 8 bits of state updates: the container reloads inside it
+    lln, mln = znorm(9, {34: -1, 1: -1, 2: -1}, 0), znorm(9, {52: -1, 1: -1, 2: -1}, 0)
+    ofn = znorm(8, {17: -1, 3: -1, 4: -1}, 2)
+    f = rle_history(ZFrame(seed=5), 160000, 1103)
+    seqs = [(2, OFF(9), 5), (32768 + 0x1ABC, (1 << 17) + 0xF0F3, 65539 + 8879), (1, OFF(13), 4), (2, OFF(2), 5)]
+    f.compressed(("raw", noise(32768 + 0x1ABC + 9, 1104), 3), seqs, ll=FSE(lln, 9), of=FSE(ofn, 8), ml=FSE(mln, 9))
+    add("sequence_of_74_bits", f)
+    assert {("ll", 9, 9), ("ml", 9, 9), ("of", 8, 8)} <= set(f.info["cell_bits"])
+
+    # --------------------------------------------------------------------------------------- sequence counts
+    add("sequences_0_with_literals", ZFrame().compressed(("raw", text[:29], 1), []))
+    add("sequences_0_without_literals", ZFrame().raw(h8).compressed(("raw", b"", 1), []).rle(1, 2))
+    add("sequences_0_without_literals_only_block", ZFrame().compressed(("raw", b"", 1), []))
+    add("sequences_1", ZFrame().compressed(("raw", text[:29], 1), [(9, OFF(4), 11)]))
+    for n in (127, 128, 300):
+        seqs = [(1, OFF(1 + i % 3), 3 + i % 5) for i in range(n)]
+        add(f"sequences_{n}", ZFrame(seed=n).compressed(("raw", noise(n + 4, 1110 + n), 2), seqs))
+    add("sequences_5_in_2_byte_count", ZFrame().compressed(("raw", text[:29], 1), [(3, OFF(2), 4)] * 5, count_bytes=2))
+    add("sequences_127_in_2_byte_count", ZFrame().compressed(("raw", noise(127, 1115), 2), [(1, OFF(1), 3)] * 127,
+                                                             count_bytes=2))
+    # 32512 sequences of 0 bits each (all tables RLE): offset value 1 without literals swaps the first two repeat
+    # offsets (1 and 4) every time
+    f = ZFrame().raw(h8).compressed(("raw", b"", 1), [(0, 1, 3)] * 32512, ll=RLE(0), of=RLE(0), ml=RLE(0))
+    assert len(f.finish()[1]) == 8 + 3 * 32512 and len(f.finish()[0]) < 40
+    add("sequences_32512_in_3_byte_count", f)
+
+    # -------------------------------------------------------------------------------------------- bitstreams
+    llb = {ZLL_BITS[c]: c for c in range(35, 0, -1)}      # the lowest code above 0 for every number of extra bits
+    mlb = {ZML_BITS[c]: c for c in range(52, -1, -1)}
+    for total in list(range(8)) + [8 * k for k in range(1, 9)] + [13, 30, 66]:
+        n, oc, lc, mc = min((n, ob, llb[lb], mlb[mb]) for n in (1, 2, 3, 4) for ob in range(10)
+                            for lb in llb if lb <= 9 for mb in mlb if mb <= 9 if n * (ob + lb + mb) == total)
+        rnd = random.Random(total)
+        seqs = [(ZLL_BASE[lc] + rnd.getrandbits(ZLL_BITS[lc]), (1 << oc) + rnd.getrandbits(oc),
+                 ZML_BASE[mc] + rnd.getrandbits(ZML_BITS[mc])) for _ in range(n)]
+        f = ZFrame().raw(ZH).compressed(("raw", noise(sum(s[0] for s in seqs), 1120 + total), 2), seqs,
+                                        ll=RLE(lc), of=RLE(oc), ml=RLE(mc))
+        assert f.info["seq_bits"] == [total] and f.info["seq_bytes"] == [total // 8 + 1], (total, f.info)
+        add(f"sequence_bitstream_of_{total}_bits", f)
+    assert cov["marker_bit"] == set(range(8)) and cov["seq_bytes"] >= set(range(1, 10))
+
+    # ---------------------------------------------------------------------------------------- repeat offsets
+    f = ZFrame().raw(h70).compressed(("raw", noise(40, 1130), 2), [
+        (4, OFF(10), 4), (1, OFF(20), 5), (2, OFF(30), 3),                  # history 30, 20, 10
+        (3, 1, 5), (2, 2, 4), (1, 3, 6),                                    # literals: idx 0, 1, 2
+        (0, 1, 3), (0, 2, 4), (0, 3, 5),                                    # none: idx 1, 2, 3 (rep0 - 1)
+        (0, 3, 7), (5, 1, 3), (0, 1, 9), (0, 2, 4), (1, 3, 3), (0, 3, 4)])
+    assert f.info["rep_idx"] == {0, 1, 2, 3}
+    add("repeat_offsets_every_index", f)
+    f = ZFrame().raw(h70).compressed(("raw", text[:20], 1), [(4, OFF(10), 4), (1, OFF(20), 5), (2, OFF(33), 3)])
+    f.raw(b"raw block").compressed(("raw", text[:20], 1), [(3, 2, 5), (0, 2, 4)])
+    f.rle(0x5F, 21).compressed(("raw", text[:20], 1), [(0, 3, 5), (4, 3, 4), (0, 1, 6)])
+    f.compressed(("raw", text[:20], 1), []).compressed(("raw", text[:20], 1), [(1, 3, 8), (0, 3, 3)])
+    add("repeat_offsets_across_compressed_raw_rle_blocks", f)
+    add("initial_repeat_offsets_1_4_8", ZFrame().raw(ZH[:20]).compressed(("raw", text[:20], 1),
+                                                                         [(1, 1, 5), (2, 2, 6), (3, 3, 7)]))
+    add("initial_repeat_offsets_without_literals", ZFrame().raw(ZH[:20]).compressed(
+        ("raw", text[:20], 1), [(0, 1, 5), (0, 2, 6), (0, 1, 4)]))
+    add("initial_repeat_offset_8_at_position_8", ZFrame().compressed(("raw", text[:20], 1), [(8, 3, 5)]))
+
+    # --------------------------------------------------------------------------------------- match execution
+    lens = (3, 31, 32, 33, 64, 65)
+    for off in list(range(1, 35)) + [63, 64, 65]:
+        add(f"match_offset_{off}", ZFrame(seed=off).raw(h70).compressed(
+            ("raw", noise(len(lens), 1200 + off), 1), [(1, OFF(off), m) for m in lens]))
+    for d in (0, -1, 1):
+        add(f"match_offset_equals_length{d:+d}".replace("+0", ""), ZFrame().raw(h70).compressed(
+            ("raw", noise(len(lens), 1240 + d), 1), [(1, OFF(m + d), m) for m in lens]))
+    add("match_chain_of_45", ZFrame().raw(h8).compressed(
+        ("raw", noise(23, 1250), 1), [((i % 2), OFF(4 - i % 2), 4 + i % 4) for i in range(45)]))
+    add("match_chain_of_45_rle_tables", ZFrame().raw(h8).compressed(
+        ("raw", b"", 1), [(0, OFF(5), 4)] * 45, ll=RLE(0), of=RLE(3), ml=RLE(1)))
+    add("match_source_straddles_completed_output", ZFrame().raw(h70).compressed(
+        ("raw", noise(12, 1251), 1), [(5, OFF(50), 10), (0, OFF(12), 8), (3, OFF(40), 33), (0, OFF(35), 34),
+                                      (4, OFF(70), 3), (0, OFF(5), 40)]))
+    add("match_reads_literals_of_its_own_sequence", ZFrame().raw(h8).compressed(
+        ("raw", noise(31, 1252), 1), [(8, OFF(4), 6), (20, OFF(20), 45), (3, OFF(1), 33)]))
+
+    # ------------------------------------------------------------------------------------------ tail staging
+    w5 = huf_chain(5, [0x65, 0x20, 0x74, 0x61, 0x6F, 0x6E])
+    d = huf_data(w5, 500, 1260)
+    for streams, sf in ((1, 0), (4, 1)):
+        for pos in (0, 250, 500):
+            add(f"huffman_{streams}_stream_block_with_one_match_at_{pos}",
+                ZFrame().raw(h8).compressed(("huf", d, w5, streams, sf, "direct"), [(pos, OFF(5), 3)]))
+        add(f"huffman_{streams}_stream_third_block", ZFrame().raw(h8).rle(0x20, 40).compressed(
+            ("huf", d, w5, streams, sf, "direct"), [(17, OFF(45), 30), (400, 1, 3)]).raw(b"tail"))
+
+    # --------------------------------------------------------------------------------------------- malformed
+    ok = lambda: ZFrame().raw(h16).compressed(("raw", text[:20], 1), [(4, OFF(3), 5)])      # noqa: E731
+    bad("bad_magic", ok(), "z_header", 64, magic=ZSTD_MAGIC ^ 0x100)
+    bad("reserved_descriptor_bit", ok(), "z_header", 64, fhd_or=8)
+    for did in (1, 2, 4):
+        bad(f"dictionary_id_in_{did}_bytes", ZFrame(did=did).raw(h16), "z_header", 64, did_value=1 << (8 * did - 1))
+    f = ZFrame(did=1, fcs=8).raw(h16)
+    comp = f.finish()[0]
+    assert f.header_len == 15
+    for cut in range(1, 15):
+        bad(f"header_cut_to_{cut}_bytes", comp, "z_header" if cut < 6 else "trunc", 64, cut=cut)
+    f = ok()
+    f.blocks.append((3, 5, b"12345"))
+    bad("reserved_block_type", f, "z_block", 64)
+    bad("raw_block_cut_short", ZFrame().raw(h16), "trunc", 64, cut=6 + 3 + 10)
+    bad("rle_block_without_its_byte", ZFrame().raw(h16).rle(7, 5), "trunc", 64, cut=6 + 3 + 16 + 3)
+    comp = ok().finish()[0]
+    bad("compressed_block_cut_short", comp, "z_block", 64, cut=len(comp) - 2)
+    bad("block_header_cut_short", comp, "trunc", 64, cut=6 + 3 + 16 + 2)
+    bad("no_last_block", ok(), "trunc", 64, no_last=True)
+    bad("compressed_block_larger_than_window", ZFrame(window=(0, 0)).compressed(("raw", noise(1022, 1300), 2), []),
+        "z_block", 2048)
+    bad("block_regenerates_more_than_window", ZFrame(window=(0, 0)).compressed(
+        ("raw", text[:20], 1), [(10, OFF(1), 1015)]), "z_block", 1100)
+    bad("block_regenerates_more_than_128_kib", ZFrame().raw(h16).compressed(
+        ("rle", 0x11, ZBLOCK_MAX, 3), [(0, OFF(1), 3)]), "z_block", ZBLOCK_MAX + 32)
+    # ---- literals
+    bad("literals_regenerate_more_than_128_kib", ZFrame().compressed(("rle", 0x11, ZBLOCK_MAX + 1, 3), []),
+        "z_lit", ZBLOCK_MAX + 8)
+    bad("literals_raw_longer_than_block", ZFrame().compressed(("raw", text[:20], 1), [], size=15), "z_lit", 64)
+    d = huf_data(w4, 100, 1310)
+    bad("literals_compressed_size_past_block", ZFrame().compressed(
+        ("huf", d, w4, 1, 0, "direct", {"csize_delta": 2}), []), "z_lit", 100)
+    bad("literals_jump_table_larger_than_section", ZFrame().compressed(
+        ("huf", d, w4, 4, 1, "direct", {"jump": [9, 9, 30]}), []), "z_lit", 100)
+    bad("literals_4_streams_without_jump_table", ZFrame().compressed(
+        ("huf", d, w4, 4, 1, "direct", {"body": lambda b: b[:5]}), []), "z_lit", 100)
+    f = ZFrame().compressed(("raw", text[:20], 1), [])
+    f.huf = huf_codes(w4)
+    bad("treeless_literals_without_tree", f.compressed(("treeless", d, 1, 0), []), "z_huf", 120)
+    tree = lambda ws: {"tree": huf_tree_direct(ws)}                                       # noqa: E731
+    bad("huffman_weight_12", ZFrame().compressed(("huf", d, w4, 1, 0, "direct", tree([12, 1, 1])), []), "z_huf", 100)
+    bad("huffman_weights_leave_no_power_of_two", ZFrame().compressed(
+        ("huf", d, w4, 1, 0, "direct", tree([3, 1])), []), "z_huf", 100)
+    bad("huffman_weights_sum_to_0", ZFrame().compressed(("huf", d, w4, 1, 0, "direct", tree([0, 0])), []),
+        "z_huf", 100)
+    bad("huffman_tree_cut_short", ZFrame().compressed(
+        ("huf", b"", w4, 1, 0, "direct", {"tree": huf_tree_direct([1] * 127)[:20]}), []), "z_huf", 100)
+    bad("huffman_stream_ends_with_zero_byte", ZFrame().compressed(
+        ("huf", d, w4, 1, 0, "direct", {"body": lambda b: b[:-1] + b"\x00"}), []), "z_huf", 100)
+    bad("huffman_1_of_4_streams_ends_with_zero_byte", ZFrame().compressed(
+        ("huf", d, w4, 4, 1, "direct", {"body": lambda b: b[:-1] + b"\x00"}), []), "z_huf", 100)
+    for streams, sf in ((1, 0), (4, 1)):
+        bad(f"huffman_{streams}_stream_one_symbol_short", ZFrame().compressed(
+            ("huf", d, w4, streams, sf, "direct", {"regen_delta": 1}), []), "z_huf", 101)
+        bad(f"huffman_{streams}_stream_one_symbol_long", ZFrame().compressed(
+            ("huf", d, w4, streams, sf, "direct", {"regen_delta": -1}), []), "z_huf", 100)
+    wf = huf_chain(3, [0x30, 0x31, 0x33, 0x34])
+    bad("huffman_weight_fse_accuracy_7", ZFrame().compressed(
+        ("huf", huf_data(wf, 100, 1311), wf, 1, 0, "direct",
+         {"tree": huf_tree_fse(wf[:-1], 6, log_field=2)}), []), "z_huf", 100)
+    # ---- FSE descriptions
+    a = [(2, OFF(5), 5), (1, OFF(13), 3)]
+
+    def fse_bad(name, kind, desc, ends_block=False):
+        """The sequences ``a`` behind the description ``desc`` of the table of ``kind`` (the other two predefined);
+        ``ends_block``: the block ends with the description."""
+        modes = {k: FSE(fse_ok[k], 5, desc) if k == kind else PRE for k in ZSTD_KINDS}
+        f = ZFrame().raw(h70).compressed(("raw", text[:9], 1), a, tail=b"" if ends_block else None, **modes)
+        bad(name, f, "z_fse", 100)
+
+    fse_ok = {"ll": znorm(5, {0: 8, 2: 8}, 1), "of": znorm(5, {3: 8}, 4), "ml": znorm(5, {0: 8, 2: 8}, 1)}
+
+    for kind in ZSTD_KINDS:
+        mx, top = ZSTD_MAX_LOG[kind], ZSTD_MAX_SYM[kind]
+        d = FseDesc(mx + 1)
+        d.count(1 << mx).count(1 << mx)
+        fse_bad(f"fse_{kind}_accuracy_{mx + 1}", kind, d.finish())
+        # (a count can never overshoot the total: the field's largest value is what remains.  What a description
+        # can do is run out of symbols before the total is reached.)
+        d = FseDesc(6)
+        for _ in range(top + 1):                           # one per symbol: 64 is not reached at the last symbol
+            d.count(1)
+        fse_bad(f"fse_{kind}_counts_stop_short_of_total", kind, d.finish() + b"\x00\x00")
+        d = FseDesc(6)
+        for _ in range(top + 1):
+            d.count(1)
+        d.count(63 - top)
+        fse_bad(f"fse_{kind}_symbol_beyond_maximum", kind, d.finish())
+        d = FseDesc(5).count(16).count(0).zeros(top).count(16)               # the run ends one past the last symbol
+        fse_bad(f"fse_{kind}_zero_run_past_maximum", kind, d.finish())
+        d = FseDesc(5).count(16).count(0).zeros(top + 30).count(16)
+        fse_bad(f"fse_{kind}_long_zero_run_past_maximum", kind, d.finish())
+        desc = fse_description(fse_ok[kind], 5)            # a good description without its last byte
+        fse_bad(f"fse_{kind}_description_cut_short", kind, desc[:-1], ends_block=True)
+        modes = {k: RLE(top + 1) if k == kind else RLE(2) for k in ZSTD_KINDS}
+        bad(f"fse_{kind}_rle_symbol_{top + 1}", ZFrame().raw(h70).compressed(
+            ("raw", text[:9], 1), [(2, OFF(5), 5)], tail=b"\x01", **modes), "z_fse", 100)
+        modes = {k: REP if k == kind else PRE for k in ZSTD_KINDS}
+        f = ZFrame().raw(h70)
+        f.tabs = {k: (fse_table(*ZSTD_DEFAULTS[k]), ZSTD_DEFAULTS[k][1]) for k in ZSTD_KINDS}
+        bad(f"fse_{kind}_repeat_without_table", f.compressed(("raw", text[:9], 1), a, **modes), "z_fse", 100)
+    # ---- sequences
+    s2 = [(4, OFF(3), 5), (18, OFF(9), 36)]
+    bad("sequence_modes_reserved_bits", ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2, reserved=1),
+        "z_seq", 150)
+    comp = ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2).finish()[0]
+    bad("sequence_stream_ends_with_zero_byte", comp[:-1] + b"\x00", "z_seq", 150)
+    bad("sequence_stream_with_1_bit_left_over", ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2, pad_low=1),
+        "z_seq", 150)
+    bad("sequence_stream_with_9_bits_left_over", ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2, pad_low=9),
+        "z_seq", 150)
+    bad("sequence_stream_1_bit_short", ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2, drop_low=1),
+        "z_seq", 150)
+    bad("sequence_section_missing", ZFrame().raw(h70).compressed(("raw", text[:30], 1), [], size=31), "trunc", 150)
+    bad("sequence_count_cut_short", ZFrame().raw(h70).compressed(("raw", text[:30], 1), [], tail=b"",
+                                                                 count_bytes=2, size=32), "trunc", 150)
+    bad("sequence_modes_missing", ZFrame().raw(h70).compressed(("raw", text[:30], 1), s2, size=32), "trunc", 150)
+    bad("literal_length_larger_than_literals_left", ZFrame().raw(h70).compressed(
+        ("raw", text[:30], 1), [(4, OFF(3), 5), (27, OFF(9), 6)]), "overflow", 150)
+    # ---- offsets
+    bad("offset_one_past_output", ZFrame().raw(h16).compressed(("raw", text[:9], 1), [(4, OFF(21), 5)]),
+        "offset", 64)
+    bad("offset_one_past_output_first_block", ZFrame().compressed(("raw", text[:9], 1), [(4, OFF(5), 5)]),
+        "offset", 64)
+    bad("offset_0_from_repeat_offset_1_minus_1", ZFrame().raw(h16).compressed(("raw", text[:9], 1), [(0, 3, 5)]),
+        "offset", 64)
+    bad("initial_repeat_offset_4_at_position_2", ZFrame().compressed(("raw", text[:9], 1), [(2, 2, 5)]),
+        "offset", 64)
+    bad("initial_repeat_offset_8_at_position_7", ZFrame().compressed(("raw", text[:9], 1), [(7, 3, 5)]),
+        "offset", 64)
+    # offset code 31 with every extra bit set is offset 2^32 - 4: as a signed 32-bit number, -4.  The slot has 8
+    # bytes after the write position, so a decoder that takes it for -4 still reads its own slot.
+    bad("offset_code_31_extra_all_ones", ZFrame().compressed(
+        ("raw", noise(30, 1320), 1), [(30, (1 << 32) - 1, 3)], of=RLE(31)), "offset", 30 + 3 + 8)
+    bad("offset_code_31_extra_zero", ZFrame().compressed(
+        ("raw", noise(30, 1321), 1), [(30, 1 << 31, 3)], of=RLE(31)), "offset", 30 + 3 + 8)
+    bad("offset_code_30_extra_all_ones", ZFrame().compressed(
+        ("raw", noise(30, 1322), 1), [(30, (1 << 31) - 1, 3)], of=RLE(30)), "offset", 30 + 3 + 8)
+    # ---- capacity: well-formed frames, one byte more than the slot
+    for name, f in (("raw_block", ZFrame().raw(h16).raw(h70)), ("rle_block", ZFrame().raw(h16).rle(3, 70)),
+                    ("match", ZFrame().raw(h16).compressed(("raw", text[:9], 1), [(9, OFF(3), 40)])),
+                    ("long_match", ZFrame().raw(h16).compressed(("raw", text[:9], 1), [(9, OFF(3), 400)]))):
+        comp, out = f.finish()
+        bad(f"capacity_one_short_in_{name}", comp, "overflow", len(out) - 1, True)
+    for delta in (1, -1):
+        for fcs, window in ((1, None), (2, (10, 0)), (4, (10, 0)), (8, None)):
+            f = ZFrame(window=window, fcs=fcs).raw(ZH[:300] if fcs > 1 else h70).compressed(
+                ("raw", text[:9], 1), [(9, OFF(3), 40)])
+            bad(f"fcs_{fcs}_bytes_content{delta:+d}", f, "size", len(f.finish()[1]), fcs_delta=delta)
+    return tuple(V), tuple(B), cov
 
 
 # =====================================================================================================================

@@ -1,11 +1,15 @@
 // Native self-check of the host codecs, built with AddressSanitizer + UBSan by tests/test_native_sanitizers.py:
 // Kafka record-batch encode → decode round trips for every codec (incl. truncated and corrupted input), CRC-32C
-// vectors, LZ4 frame round trips plus decoding of random garbage / truncated frames, and the Java double formatter.  Exit code 0 = clean.
+// vectors, LZ4 frame round trips plus decoding of random garbage / truncated frames, and the Java double formatter.
+// With a file argument, the zstd decoder also takes every record of that file (tests/codec_vectors.py's hand-built
+// frames): int64 expected length (-1: malformed), int64 capacity, int64 frame length, the frame, the expected bytes.
+// Exit code 0 = clean.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -184,7 +188,45 @@ static void oversized_declared_sizes() {
   }
 }
 
-int main() {
+// Every frame and every output buffer is a heap block of exactly its size, so a read or write one byte outside is
+// reported.  A valid frame must decode to its bytes (also into a larger buffer); a malformed one must return < 0.
+static void zstd_vector_file(const char* path) {
+  std::FILE* f = std::fopen(path, "rb");
+  CHECK(f != nullptr);
+  if (!f) return;
+  int64_t head[3];
+  int64_t records = 0;
+  while (std::fread(head, sizeof(int64_t), 3, f) == 3) {
+    const int64_t want = head[0], cap = head[1], flen = head[2];
+    CHECK(want >= -1 && cap >= 0 && flen >= 0 && flen < (1 << 24) && cap < (1 << 24));
+    if (failures) break;
+    std::vector<uint8_t> frame((size_t)flen), expected((size_t)(want > 0 ? want : 0));
+    CHECK(std::fread(frame.data(), 1, frame.size(), f) == frame.size());
+    CHECK(std::fread(expected.data(), 1, expected.size(), f) == expected.size());
+    for (int64_t extra : {0, 37}) {
+      if (want < 0 && extra) continue;
+      std::unique_ptr<uint8_t[]> out(new uint8_t[(size_t)(cap + extra)]);      // (not null for a capacity of 0)
+      const int64_t r = dxa_zstd_decompress(frame.data(), flen, out.get(), cap + extra);
+      if (want < 0) {
+        CHECK(r < 0);
+        if (r >= 0) std::fprintf(stderr, "record %lld: malformed frame decoded to %lld bytes\n", (long long)records,
+                                 (long long)r);
+      } else {
+        CHECK(r == want);
+        CHECK(r != want || want == 0 || std::memcmp(out.get(), expected.data(), (size_t)want) == 0);
+        if (r != want) std::fprintf(stderr, "record %lld: %lld, expected %lld\n", (long long)records, (long long)r,
+                                    (long long)want);
+      }
+    }
+    ++records;
+  }
+  std::fclose(f);
+  CHECK(records > 0);
+  std::printf("zstd vectors: %lld records\n", (long long)records);
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) zstd_vector_file(argv[1]);
   snappy_zstd_checks(5u);
   oversized_declared_sizes();
   CHECK(dxa_crc32c((const uint8_t*)"123456789", 9) == 0xE3069283u);

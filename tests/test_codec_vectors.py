@@ -1,11 +1,13 @@
-"""Device inflate / LZ4 / snappy decoders on hand-assembled streams (``tests/codec_vectors.py``).
+"""Device inflate / LZ4 / snappy / zstd decoders on hand-assembled streams (``tests/codec_vectors.py``).
 
-The CPU tests prove every vector first: zlib, pyarrow, an independent pure-Python LZ4 decoder and this project's
-host decoders must all expand a valid vector to the bytes the builder's own expansion gives, and must all reject a
-malformed one.  The GPU tests then put all vectors of a codec into one block table, shuffled (so the four 16-lane
-groups of a wave take different paths) and in order, and call the kernels' entry points directly.  Every output slot
-lies between 0xA5 guards: a decoder that writes outside its slot, or past the bytes it reports, fails an assertion.
-Any change to ``lz4.hip``, ``inflate.hip`` or ``snappy.hip`` must keep this file green.
+The CPU tests prove every vector first: zlib, pyarrow (whose zstd codec is libzstd), an independent pure-Python LZ4
+decoder and this project's host decoders must all expand a valid vector to the bytes the builder's own expansion
+gives, and must all reject a malformed one.  The GPU tests then put all vectors of a codec into one block table,
+shuffled (so the lane groups that share a wave, four of 16 lanes or two zstd frames of 32, take different paths) and
+in order, and call the kernels' entry points directly.  Every output slot lies between 0xA5 guards: a decoder that
+writes outside its slot, or past the bytes it reports, fails an assertion (``zstd.hip`` stages Huffman literals in
+the tail of its slot, so it may write anywhere inside the capacity it is given, and nowhere else).
+Any change to ``lz4.hip``, ``inflate.hip``, ``snappy.hip`` or ``zstd.hip`` must keep this file green.
 """
 import random
 import zlib
@@ -26,8 +28,12 @@ EXTRA_CAP = 37
 # status classes the three kernels' enums share (truncated / offset or distance / overflow / size), inflate's block
 # error, and inflate's code errors (10 + which check)
 KLASS = {"trunc": lambda s: s == 1, "offset": lambda s: s == 2, "overflow": lambda s: s == 3,
-         "size": lambda s: s == 4, "block": lambda s: s == 6, "code": lambda s: s >= 10}
-COUNTS = {"inflate": (45, 21), "lz4": (1364, 16), "snappy": (91, 20), "zlib": 208}
+         "size": lambda s: s == 4, "block": lambda s: s == 6, "code": lambda s: s >= 10,
+         # zstd.hip's own classes: frame header, Huffman tree or stream, FSE table, sequence section, literals
+         # section, block
+         "z_header": lambda s: s == 5, "z_huf": lambda s: s == 6, "z_fse": lambda s: s == 7,
+         "z_seq": lambda s: s == 8, "z_lit": lambda s: s == 9, "z_block": lambda s: s == 10}
+COUNTS = {"inflate": (45, 21), "lz4": (1364, 16), "snappy": (91, 20), "zlib": 208, "zstd": (334, 98)}
 
 
 # ======================================================================================================== CPU tests
@@ -36,17 +42,26 @@ def test_vector_counts():
     iv, ib = CV.inflate_vectors()
     lv, lb, relaxed = CV.lz4_vectors()
     sv, sb = CV.snappy_vectors()
+    zv, zb, _ = CV.zstd_vectors()
     got = {"inflate": (len(iv), len(ib)), "lz4": (len(lv), len(lb)), "snappy": (len(sv), len(sb)),
-           "zlib": len(CV.zlib_streams())}
+           "zlib": len(CV.zlib_streams()), "zstd": (len(zv), len(zb))}
     print("codec vectors (valid, malformed):", got)
     assert got == COUNTS
     shapes = len(CV.LZ4_LITERAL_SHAPES) + len(CV.LZ4_MATCH_SHAPES)
     assert sum(v.name.startswith("sweep_") for v in lv) == shapes * len(CV.LZ4_PREFIXES) - 1    # lit0 at P0
     assert sum(v.name.startswith("chain_") for v in lv) == len(CV.LZ4_CHAIN_SHAPES) * 67
     assert len(relaxed) == 3
-    for vs in (iv, ib, lv, lb, sv, sb, CV.zlib_streams()):
+    for vs in (iv, ib, lv, lb, sv, sb, CV.zlib_streams(), zv, zb):
         assert len({v.name for v in vs}) == len(vs)
     assert max(len(v.expected) for v in iv + lv + sv + CV.zlib_streams()) <= 71000
+    assert max(len(v.expected) for v in zv) == (1 << 20) - 1            # offset code 19 with every extra bit set
+    assert sum(len(v.expected) < 4096 for v in zv) > 0.8 * len(zv)
+
+
+def test_noise_is_not_one_repeated_byte():
+    """Match sources are cut from it: over a run of one byte every offset copies the same thing."""
+    assert len(set(CV.noise(4096, 1))) == 256 and CV.noise(64, 1) != CV.noise(64, 2)
+    assert CV.noise(64, 1)[:32] == CV.noise(32, 1)
 
 
 def test_bit_writer_and_canonical_codes():
@@ -149,6 +164,74 @@ def test_snappy_malformed_vectors_rejected_by_host_decoder():
                 K.snappy_decompress(b.comp)
 
 
+def test_zstd_writers():
+    """The checksum against XXH64's published value for the empty input (libzstd verifies it on every frame that has
+    one), the shortest frame against the 9 bytes libzstd writes for no input, and what the writers covered."""
+    assert CV.xxh64(b"") == 0xEF46DB3751D8E999
+    assert CV.ZFrame(window=None, fcs=1).raw(b"").finish()[0] == bytes.fromhex("28b52ffd2000010000")
+    assert CV.fse_description(CV.LL_DEF, 6)[0] & 15 == 1 and len(CV.fse_table(CV.ML_DEF, 6)) == 64
+    # RFC 8878 3.1.1.3.2.1.1: the sequence count's three forms
+    f = CV.ZFrame()
+    assert f._sequences([], b"", {}) == b"\x00" and f._sequences([], b"", {}, count_bytes=2) == b"\x80\x00"
+    _, _, cov = CV.zstd_vectors()
+    assert cov["marker_bit"] == set(range(8)) and cov["seq_bytes"] >= set(range(1, 10))
+    assert cov["rep_idx"] == {0, 1, 2, 3} and cov["huf_depth"] == set(range(1, 12))
+    assert cov["zero_runs"] >= {0, 1, 2, 3, 4, 24, 30}
+    assert {1, 6, 8, 13} <= cov["huf_stream_bytes"]
+    for kind, top in (("ll", 9), ("of", 8), ("ml", 9)):
+        for log in range(5, top + 1):
+            assert {(kind, log, log), (kind, log, 0)} <= cov["cell_bits"], (kind, log)
+
+
+def test_zstd_vectors_decode_with_libzstd_and_host_decoder():
+    pa = pytest.importorskip("pyarrow")
+    codec = pa.Codec("zstd")
+    valid, _, _ = CV.zstd_vectors()
+    for v in valid:
+        assert codec.decompress(v.comp, decompressed_size=len(v.expected), asbytes=True) == v.expected, v.name
+        assert K.zstd_decompress(v.comp) == v.expected, v.name
+
+
+def test_zstd_malformed_vectors_rejected_by_libzstd_and_host_decoder():
+    pa = pytest.importorskip("pyarrow")
+    codec = pa.Codec("zstd")
+    _, malformed, _ = CV.zstd_vectors()
+    for b in malformed:
+        assert b.expected is None and b.klass in KLASS
+        if b.stream_ok:                                   # a well-formed frame of one byte more than the capacity
+            assert len(codec.decompress(b.comp, decompressed_size=b.cap + 1, asbytes=True)) == b.cap + 1, b.name
+            assert len(K.zstd_decompress(b.comp)) == b.cap + 1, b.name
+        else:
+            with pytest.raises(K.KafkaError):
+                K.zstd_decompress(b.comp)
+        with pytest.raises(OSError):                      # (pyarrow also refuses any size but the one it is given)
+            codec.decompress(b.comp, decompressed_size=b.cap, asbytes=True)
+        if not b.stream_ok:                               # ... so let it try the sizes around the capacity too
+            for size in (b.cap + 1, max(b.cap - 1, 0), b.cap + 8, 1 << 18):
+                with pytest.raises(OSError):
+                    codec.decompress(b.comp, decompressed_size=size, asbytes=True)
+
+
+def test_zstd_offset_code_31_vector_separates_the_signed_from_the_unsigned_check():
+    """The index arithmetic of ``zstd.hip``'s match copy on the offset-code-31 vector.  Compared as a signed 32-bit
+    number the offset 2^32 - 4 is -4 and passes ``offset > position``; the copy then reads three bytes 4 after the
+    write position (C's ``c % -4`` is ``c`` for c < 4) and writes three at it, all inside the vector's own slot, and
+    the frame ends with status 0.  So of all malformed vectors, this one alone tells the two checks apart, and a
+    decoder with the signed check fails on its status, not on a guard."""
+    _, malformed, _ = CV.zstd_vectors()
+    by_name = {b.name: b for b in malformed}
+    b = by_name["offset_code_31_extra_all_ones"]
+    op, ml, off = 30, 3, (1 << 32) - 4                    # after the 30 literals; the vector's sequence
+    signed = off - (1 << 32)
+    assert signed == -4 and not signed > op and off > op  # the signed check passes it, the unsigned one does not
+    src = [op - signed + c for c in range(ml)]            # c % -4 == c
+    assert min(src) >= 0 and max(src) < b.cap and op + ml <= b.cap
+    # every other malformed offset is below 2^31: both comparisons reject it
+    assert b.comp[-8:-6] == bytes([0x10, 31])             # modes: the offset table is RLE, with symbol 31
+    for name, off in (("offset_code_31_extra_zero", (1 << 31) - 3), ("offset_code_30_extra_all_ones", (1 << 31) - 4)):
+        assert name in by_name and 30 < off < (1 << 31)
+
+
 # ======================================================================================================== GPU tests
 class Entry(NamedTuple):
     name: str
@@ -224,11 +307,12 @@ def _decode_into(gpu, entry_point, kind, entries, readable, src_fill):
     return t, t.results()
 
 
-def _check_memory(t, out):
-    """Only [slot, slot + true size) of a valid vector and [slot, slot + capacity) of a malformed one may change."""
+def _check_memory(t, out, whole_slot=False):
+    """Only [slot, slot + true size) of a valid vector and [slot, slot + capacity) of a malformed one may change;
+    ``whole_slot``: a valid vector's whole capacity too (a decoder that uses its slot as scratch space)."""
     frozen = np.ones(t.total, dtype=bool)
     for e, o in zip(t.entries, t.oo):
-        frozen[o:o + (len(e.expected) if e.expected is not None else e.cap)] = False
+        frozen[o:o + (len(e.expected) if e.expected is not None and not whole_slot else e.cap)] = False
     touched = np.flatnonzero(frozen & (out != FILL))
     if touched.size:
         q = int(touched[0])
@@ -238,8 +322,8 @@ def _check_memory(t, out):
                              f"(slot of {lo.name!r} at {t.oo[max(i, 0)]} cap {lo.cap}; next slot {hi.name!r})")
 
 
-def _check(t, status, produced, out, valid_status=0, check_produced=True):
-    _check_memory(t, out)
+def _check(t, status, produced, out, valid_status=0, check_produced=True, whole_slot=False):
+    _check_memory(t, out, whole_slot)
     raw = out.tobytes()
     for i, (e, o) in enumerate(zip(t.entries, t.oo)):
         what = (e.name, e.align, i)
@@ -394,3 +478,35 @@ def test_device_decodes_pyarrow_snappy_blocks(gpu):
     entries = _entries(_pyarrow_blocks("snappy"), (), (0, 1, 2, 3))
     t, (status, produced, out) = _decode_into(gpu, "dxa_snappy_decode_into", 3, entries, 0, 0xEE)
     _check(t, status, produced, out)
+
+
+# ---- zstd
+def _zstd_entries(valid, malformed, extra_cap=0):
+    return _entries(valid, malformed, (0, 1, 2, 3), extra_cap)
+
+
+def _zstd_run(gpu, entries):
+    return _decode_into(gpu, "dxa_zstd_decode_into", 4, entries, 0, 0xEE)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", ["shuffled", "original"])
+def test_device_zstd_vectors(gpu, order):
+    valid, malformed, _ = CV.zstd_vectors()
+    t, (status, produced, out) = _zstd_run(gpu, _ordered(_zstd_entries(valid, malformed), order))
+    _check(t, status, produced, out, whole_slot=True)
+
+
+@pytest.mark.gpu
+def test_device_zstd_reports_true_size_for_larger_capacity(gpu):
+    """The Kafka case: a capacity slot larger than the frame's content, with or without a content size in the
+    header."""
+    valid, _, _ = CV.zstd_vectors()
+    t, (status, produced, out) = _zstd_run(gpu, _ordered(_zstd_entries(valid, (), EXTRA_CAP), "shuffled"))
+    _check(t, status, produced, out, whole_slot=True)
+
+
+@pytest.mark.gpu
+def test_device_decodes_pyarrow_zstd_frames(gpu):
+    t, (status, produced, out) = _zstd_run(gpu, _entries(_pyarrow_blocks("zstd"), (), (0, 1, 2, 3)))
+    _check(t, status, produced, out, whole_slot=True)

@@ -6,7 +6,9 @@ both codecs (KafkaStreamingFactory.scala:70-74).  Oracles: the system libzstd co
 producer would write (no content size, no checksum) and our decoders must return the input; frames and blocks
 hand-assembled here from the format descriptions check the decoders independently of any encoder; pyarrow's
 bundled snappy / zstd / lz4 codecs (independent implementations) are a second oracle on the host and the GPU; the GPU
-decode is compared with the host decode of the same fetch."""
+decode is compared with the host decode of the same fetch.  The format-level gate of zstd.hip (every table form,
+code, mode and malformed class, on hand-built frames) is tests/test_codec_vectors.py; the FSE table builder and the
+backward bit writer used here live in tests/codec_vectors.py."""
 import json
 import random
 
@@ -16,6 +18,9 @@ import torch
 
 from dxa.io import kafka as K
 from dxa.io import kafka_device as KD
+from tests.codec_vectors import LL_DEF, ML_DEF, OF_DEF
+from tests.codec_vectors import BackWriter as _BackWriter
+from tests.codec_vectors import fse_table as _fse_table
 
 
 def _values(n, seed=0):
@@ -69,55 +74,6 @@ def test_snappy_host_round_trip_raw_and_xerial():
             z = K.snappy_compress(data, xerial)
             assert K.snappy_decompress(z) == data
     assert K.snappy_compress(b"hello", True)[:8] == b"\x82SNAPPY\x00"
-
-
-def _fse_table(norm, log):
-    """RFC 8878 4.1.1 decoding table of a normalized distribution: [(symbol, nbits, baseline)] per state."""
-    size = 1 << log
-    sym = [0] * size
-    high = size - 1
-    for s, c in enumerate(norm):
-        if c == -1:
-            sym[high] = s
-            high -= 1
-    step, pos = (size >> 1) + (size >> 3) + 3, 0
-    for s, c in enumerate(norm):
-        for _ in range(max(c, 0)):
-            sym[pos] = s
-            pos = (pos + step) & (size - 1)
-            while pos > high:
-                pos = (pos + step) & (size - 1)
-    nxt = [1 if c == -1 else c for c in norm]
-    cells = []
-    for c in range(size):
-        s = sym[c]
-        x = nxt[s]
-        nxt[s] += 1
-        nb = log - (x.bit_length() - 1)
-        cells.append((s, nb, (x << nb) - size))
-    return cells
-
-
-LL_DEF = [4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2, 2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1,
-          -1]
-OF_DEF = [1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1]
-ML_DEF = [1, 4, 3, 2, 2, 2, 2, 2, 2] + [1] * 37 + [-1] * 7
-
-
-class _BackWriter:
-    """Bits written low to high; the decoder reads them high to low (a zstd backward bitstream)."""
-
-    def __init__(self):
-        self.v, self.n = 0, 0
-
-    def put(self, value, nbits):
-        self.v |= (value & ((1 << nbits) - 1)) << self.n
-        self.n += nbits
-
-    def finish(self):
-        self.put(1, 1)                                    # the end marker
-        nbytes = (self.n + 7) // 8
-        return self.v.to_bytes(nbytes, "little")
 
 
 def _hand_frame():
