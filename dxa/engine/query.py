@@ -954,9 +954,12 @@ def _paned_aggregate(sel: A.Select, t, alias: str, ctx) -> Optional[Table]:
         # COUNT(DISTINCT x) has no mergeable partial, but the dense ring answers it (window_dense.py): a statement
         # whose aggregates are decomposable apart from one-argument distinct counts is tried there and nowhere else
         # — and so are max_by / min_by, whose state (a row pick) the ring keeps per pane and group: the aggregates
-        # only the ring can answer
+        # only the ring can answer.  The rest of the DISTINCT family rides on the same pair states: SUM / AVG(DISTINCT
+        # x), count(DISTINCT a, b, …) and approx_count_distinct (here the exact distinct count)
         dcounts = {k: c for k, c in aggs.items() if c.name not in ctx.udafs and (
-            (c.distinct and c.name == "count" and len(c.args) == 1 and not c.star) or
+            (c.distinct and c.name == "count" and len(c.args) >= 1 and not c.star) or
+            (c.distinct and c.name in ("sum", "avg") and len(c.args) == 1) or
+            (c.name == "approx_count_distinct" and not c.distinct and len(c.args) in (1, 2)) or
             (c.name in ("max_by", "min_by") and not c.distinct and len(c.args) == 2))}
         dense_only = bool(dcounts)
         ok = ok and D.decomposable({k: c for k, c in aggs.items() if k not in dcounts}, ctx)

@@ -16,7 +16,8 @@ window flow host-bound.  Here the state a window needs lives in HBM in the shape
   synchronisation — and builds the output columns as views of the dictionary and the finished aggregates.
 
 Eligible: GROUP BY statements whose aggregates are COUNT / SUM / MIN / MAX / AVG over numeric (decimals
-included, below), boolean or timestamp arguments (and COUNT(DISTINCT x), the variance family and corr / covar_pop /
+included, below), boolean or timestamp arguments (and COUNT / SUM / AVG(DISTINCT x), count(DISTINCT a, b, …) and
+approx_count_distinct, the variance family and corr / covar_pop /
 covar_samp / skewness / kurtosis, below; count_if; bool_and / every, bool_or / any / some; first / last / max_by /
 min_by, below), with plain key columns,
 deterministic, on a GPU.  With N ranks each rank's window
@@ -55,6 +56,27 @@ GROUP BY that has such a distinct count runs as one group under a constant key t
 the window passes its WHERE the one output row (counts 0, the rest NULL) is built once the status says no group was
 kept.  A distinct count has no mergeable partial: with N ranks it is answered here only over a replicated view, and
 a statement the ring declines goes to the generic path (the materialised window), never to the pane partials.
+
+**SUM / AVG(DISTINCT x), count(DISTINCT a, b, …), approx_count_distinct** are answered from the same pair states
+(``_requests(…, distinct_sums=True)``; routed like the distinct count: the ring or the generic path).  The pair
+dictionary of x holds every live pair's value in key column 1, so SUM(DISTINCT x) is the sum of that column over a
+group's live pairs: COUNT, SUM and AVG(DISTINCT x) of one x share one ``PairState`` and one fold launch,
+``win_distinct_fold_kernel<true>``, which also loads each live pair's value and adds it — reduced in the wave per
+distinct parent, then one atomic per word — into sum words of the combined row that no pane accumulates into (value
+kind -1, 0 in every pane and block slot, like the ``dcount`` word): an ``MA_ADD_U64`` word for SUM(DISTINCT integral),
+the exact wrapping ``long``, and an ``MA_ADD_F64`` word for SUM(DISTINCT float / double) and every AVG(DISTINCT x)
+(accumulated as doubles, as the plain AVG slot is).  A distinct sum or average always has x's ``dcount`` word as its
+count word, so ``win_emit_kernel``'s existing kinds finish it and a group without a non-NULL x gives NULL; a
+non-numeric x is "sum type" / "avg type", a decimal x "argument type".  The values come from the dictionary, which
+stores -0.0 as 0.0 and every NaN as the canonical one, where ``query._distinct_agg`` sums the bits of each value's
+first row: a zero sum may differ in sign from the generic path's (equal under ==).  An f64 sum's last bits depend on
+the order the atomics arrive in.  A layout without distinct sums runs the fold instantiation it always ran.
+count(DISTINCT a, b, …) of two to ``MAX_DISTINCT_COLS`` arguments ("too many distinct columns" beyond) is one pair
+state keyed by (group id, a, b, …) — the same insert kernel with more key columns; a row with a NULL in any argument
+creates no pair (the validities are ANDed once per pane) — and the count fold.  approx_count_distinct(x[, rsd]) is in
+this engine the exact distinct count (``query._eval_agg``): the ``dcount`` of x, sharing the state and the word of
+COUNT(DISTINCT x); rsd must be a constant and is ignored.  Each different argument or tuple is one of the
+``MAX_DISTINCT`` pair states.
 
 **STDDEV / VARIANCE** (``_VARIANCE``; up to ``MAX_VARIANCE`` different arguments per statement) keep, per pane and
 group, the triple (n, Σx, M2) with M2 = Σ (x − mean)² about the pane's own mean: n and Σx are the count and sum words
@@ -173,6 +195,7 @@ from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from . import decimal as Dec
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
 from .decimal import is_decimal
+from ..sql.ast import Literal
 
 DENSE_GROUPS = 1 << 16            # initial dictionary capacity per statement (groups with ids at one time)
 DENSE_GROUPS_MAX = 1 << 20        # the capacity grows to this at most (win_compact_kernel's single-workgroup scan)
@@ -181,6 +204,7 @@ BLOCK = 16                        # consecutive in-window panes pre-combined int
 DENSE_PAIRS = 1 << 16             # initial capacity of a COUNT(DISTINCT x) pair dictionary ((group, x) pairs with ids)
 DENSE_PAIRS_MAX = 1 << 20         # it grows to this at most (its presence ring is one byte per ring slot and pair)
 MAX_DISTINCT = 4                  # different distinct arguments per statement (window_ring.hip kMaxPairStates)
+MAX_DISTINCT_COLS = 4             # arguments of one count(DISTINCT a, b, …): value columns of its pair dictionary
 MAX_VARIANCE = 8                  # different STDDEV / VARIANCE arguments per statement (window_ring.hip kMaxM2Args)
 MAX_MOMENTS = 8                   # skewness / kurtosis arguments plus corr / covar pairs (window_ring.hip kMaxMomArgs)
 MAX_DECIMAL = 8                   # decimal sum arguments plus two-lane decimal MIN / MAX (window_ring.hip kMaxDecJobs)
@@ -235,6 +259,16 @@ _SUPPORTED = {"count", "sum", "min", "max", "avg", "mean", "count_if", *_VARIANC
 # (``_requests(aggs, picks=True)``; ``dense_answer`` does): the first two have a mergeable partial state, the keyed
 # ones have none and only the ring answers them (as it does COUNT(DISTINCT x))
 _RING_ONLY = ("max_by", "min_by")
+# The pair-state aggregates beyond COUNT(DISTINCT x) — SUM / AVG(DISTINCT x), count(DISTINCT a, b, …) and
+# approx_count_distinct(x[, rsd]) — are eligible only under ``_requests(aggs, distinct_sums=True)`` (``dense_answer``
+# passes it): their funcs are "dsum", "davg" and "dcount" (the last with a tuple of arguments for several columns)
+_DISTINCT = ("dcount", "dsum", "davg")
+
+
+def distinct_key(arg):
+    """The key of a pair state: the argument's key, or for count(DISTINCT a, b, …) — ``arg`` a tuple — the tuple of
+    its arguments' keys under a tag no expression key starts with."""
+    return ("dtuple", *(a.key() for a in arg)) if isinstance(arg, tuple) else arg.key()
 
 
 def pick_y_key(y):
@@ -269,7 +303,9 @@ class _EmitArgs(ctypes.Structure):
 
 class _PairFold(ctypes.Structure):
     _fields_ = [("pres", ctypes.c_void_p), ("pitch", ctypes.c_int64), ("parent", ctypes.c_void_p),
-                ("pscal", ctypes.c_void_p), ("pcap", ctypes.c_int32), ("word", ctypes.c_int32)]
+                ("pscal", ctypes.c_void_p), ("pcap", ctypes.c_int32), ("word", ctypes.c_int32),
+                ("vals", ctypes.c_void_p), ("vkind", ctypes.c_int32), ("isum", ctypes.c_int32),
+                ("fsum", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
 class _PairFolds(ctypes.Structure):
@@ -351,7 +387,7 @@ class Ineligible(Exception):
     """The statement (or this batch) is answered by the paned path."""
 
 
-def _requests(aggs: Dict, picks: bool = False):
+def _requests(aggs: Dict, picks: bool = False, distinct_sums: bool = False):
     """[(agg key, func, arg expr or None)] or Ineligible.  ``COUNT(DISTINCT x)`` with one argument is the func
     "dcount"; every other DISTINCT aggregate is ineligible, and so are more than ``MAX_DISTINCT`` different
     distinct arguments.  The variance family keeps its name (``_VARIANCE``), ``bool_and`` / ``every`` are "min" and
@@ -364,7 +400,13 @@ def _requests(aggs: Dict, picks: bool = False):
     same funcs, and the two-argument ``first(x, true)`` stays ineligible under its own name) and ``max_by`` /
     ``min_by`` (two: the arg entry is the tuple (x, y)) keep their names — all four only with ``picks``, which promises
     that the combine gets its slots in the window's row order, as ``_enqueue`` passes them; more than ``MAX_PICK``
-    different rank jobs (first, last, and one per direction and y) or payload jobs (rank job and x) are ineligible."""
+    different rank jobs (first, last, and one per direction and y) or payload jobs (rank job and x) are ineligible.
+    With ``distinct_sums`` (the caller hands ``plan_layout`` the distinct arguments' types too, and its pair states
+    take several value columns): ``SUM(DISTINCT x)`` / ``AVG(DISTINCT x)`` are "dsum" / "davg" of x,
+    ``count(DISTINCT a, b, …)`` of two to ``MAX_DISTINCT_COLS`` arguments is "dcount" of the tuple (more: "too many
+    distinct columns"), ``approx_count_distinct(x)`` / ``approx_count_distinct(x, rsd)`` with a constant rsd — which
+    is ignored, as the generic evaluator ignores it — is "dcount" of x.  Each different argument or tuple is one of the
+    ``MAX_DISTINCT`` pair states, shared by every aggregate over it."""
     out = []
     dargs = set()
     vargs = set()
@@ -372,15 +414,26 @@ def _requests(aggs: Dict, picks: bool = False):
     pranks, pvals = set(), set()
     for ak, call in aggs.items():
         name = call.name
-        if name not in _SUPPORTED and not (picks and _PICK_ALIAS.get(name, name) in _PICKS):
+        approx = distinct_sums and name == "approx_count_distinct" and not call.distinct
+        if name not in _SUPPORTED and not approx and not (picks and _PICK_ALIAS.get(name, name) in _PICKS):
             raise Ineligible(name)
-        if call.distinct:
-            if name != "count" or call.star or len(call.args) != 1:
+        if call.distinct or approx:
+            func, arg = "dcount", call.args[0] if call.args else None
+            if approx:
+                if len(call.args) not in (1, 2) or (len(call.args) == 2 and not isinstance(call.args[1], Literal)):
+                    raise Ineligible(name)
+            elif distinct_sums and name in ("sum", "avg") and len(call.args) == 1:
+                func = "d" + name
+            elif distinct_sums and name == "count" and not call.star and len(call.args) > 1:
+                if len(call.args) > MAX_DISTINCT_COLS:
+                    raise Ineligible("too many distinct columns")
+                arg = tuple(call.args)
+            elif name != "count" or call.star or len(call.args) != 1:
                 raise Ineligible(f"{name} distinct")
-            dargs.add(call.args[0].key())
+            dargs.add(distinct_key(arg))
             if len(dargs) > MAX_DISTINCT:
                 raise Ineligible("too many distinct arguments")
-            out.append((ak, "dcount", call.args[0]))
+            out.append((ak, func, arg))
             continue
         if call.star or (name == "count" and not call.args):
             out.append((ak, "count_star", None))
@@ -461,7 +514,10 @@ def _distinct_arg(c):
 
 def plan_layout(reqs, arg_types: Dict) -> Dict:
     """The accumulator layout of a statement (no device involved).  ``reqs``: ``_requests``' result;
-    ``arg_types[arg key] = (column dtype, is float64)`` of every evaluated non-distinct argument.
+    ``arg_types[arg key] = (column dtype, is float64)`` of every evaluated non-distinct argument and of the argument
+    of every SUM / AVG(DISTINCT x).  Those two share x's ``dcount`` slot as their count slot and add sum slots of value
+    kind -1 that only the distinct fold fills: ``dsum_words`` {x key: (u64 sum word, f64 sum word), -1 where absent};
+    the key is absent from a layout without them.
 
     → ``slots`` [(key, agg_multi value kind, combine op)], ``order`` (slot per word, None for padding),
     ``line_ops`` (combine op per 8-word line), ``plan`` [(agg key, kind, slot, count slot, dtype)] and beside it
@@ -546,7 +602,27 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         if func == "dcount":
             # a count word no pane accumulates into (agg_multi's "unused" spec): 0 in every pane and block
             # slot, filled per batch by win_distinct_fold_kernel and finished by F_COUNT like any count
-            agg(ak, "count", slot(("dcount", arg.key()), _MV_COUNT, _MA_ADD_F64), None, None, _F_COUNT, None)
+            agg(ak, "count", slot(("dcount", distinct_key(arg)), _MV_COUNT, _MA_ADD_F64), None, None, _F_COUNT, None)
+            continue
+        if func in ("dsum", "davg"):
+            # SUM / AVG(DISTINCT x): the sum of x over the group's live pairs, added by the distinct fold beside the
+            # count of the same pairs — the dcount word of x, which such an aggregate always has and which is its
+            # count word ("count > 0 → valid": a group without a non-NULL x gives NULL).  The sum words are words no
+            # pane accumulates into either (value kind -1): the exact wrapping int64 sum in a u64 add line for
+            # SUM(DISTINCT integral), the f64 sum for SUM(DISTINCT float / double) and for every AVG(DISTINCT x)
+            # (accumulated as doubles, as the plain AVG slot is).  No mergeable partial, as for the distinct count
+            ck = arg.key()
+            dtype = arg_types[ck][0]
+            if is_decimal(dtype):
+                raise Ineligible("argument type")
+            if dtype not in _NUMERIC:
+                raise Ineligible(f"{func[1:]} type")
+            dc = slot(("dcount", ck), _MV_COUNT, _MA_ADD_F64)
+            if func == "dsum" and dtype not in ("float", "double"):
+                agg(ak, "sum", slot(("dsumi", ck), -1, _MA_ADD_U64), dc, "long", _F_I64, None)
+            else:
+                sm = slot(("dsumf", ck), -1, _MA_ADD_F64)
+                agg(ak, func[1:], sm, dc, "double", _F_F64 if func == "dsum" else _F_AVG, None)
             continue
         if func in _PICKS:
             # a row pick: a rank word R (which row of the pane wins; shared by every pick of the same kind and y), and
@@ -715,6 +791,13 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     out = dict(slots=slots, order=order, nslots=nslots, line_ops=line_ops, stride=stride, plan=plan,
                count_word=where[star], fin=fin, pfin=pfin, m2desc=m2desc, m2args=m2args, dcount_word=dcount_word,
                as_f64=as_f64, rows=rows)
+    dsums = {}
+    for i, (key, _k, _o) in enumerate(slots):
+        if key[0] in ("dsumi", "dsumf"):
+            dsums.setdefault(key[1], [-1, -1])[key[0] == "dsumf"] = where[i]
+    if dsums:
+        # per distinct argument with a SUM / AVG(DISTINCT x): (its integer sum word, its f64 sum word), -1: none
+        out["dsum_words"] = {ck: tuple(w) for ck, w in dsums.items()}
     if dec_jobs:
         # per decimal job the words of win_dec_kernel; per low key word its high word (win_combine_kernel)
         out["decargs"] = [(ck, kind, where[w0], where[w1], -1 if w2 is None else where[w2])
@@ -754,7 +837,9 @@ class PairState:
     """One distinct argument of a statement: the persistent dictionary of its (group id, x) pairs and the presence
     ring ``pres`` — ``uint8 [ring slots][pitch]``, 1 where the slot's pane has a row of the pair.  ``pcap``: the
     dictionary's current capacity; ``rebuilds``: how often it was rebuilt (recycled, grown, or renumbered because
-    the group dictionary was)."""
+    the group dictionary was).  For count(DISTINCT a, b, …) the "pair" is the tuple (group id, a, b, …): ``keys``
+    has one value column per argument after column 0.  ``isum`` / ``fsum``: the words SUM / AVG(DISTINCT x) of this
+    argument are folded into (-1: none), read from value column 1."""
 
     def __init__(self, owner: "DenseWindow", k: int, arg_key):
         self.owner = owner
@@ -764,7 +849,7 @@ class PairState:
         self.rebuilds = 0
         self.full = False               # the last status' "pair dictionary full"
         self.scal_ptr = owner.scal.data_ptr() + 16 * (1 + k)      # this state's counter and flags in the status
-        self.word = -1
+        self.word = self.isum = self.fsum = -1
         self.keys = self.pres = None
         self._alloc_table(self.pcap)
         N.call("dxa_win_init", N.ptr(self.htab), N.ptr(self.gid_of_slot), self.hcap, N.stream_handle(owner.device))
@@ -780,33 +865,39 @@ class PairState:
 
     def _bytes(self, pcap: int) -> int:
         o = self.owner
-        x = 8 + 1 if self.keys is None or self.keys[1][1] != 2 else _sizes()[2] + 4 + 1
+        x = 8 + 1 if self.keys is None else sum((_sizes()[2] + 4 if k[1] == 2 else 8) + 1 for k in self.keys[1:])
         return (o.R + o.NB) * _pitch(pcap) + (pcap + 1) * (9 + x) + 12 * _table_slots(pcap)
 
-    def build(self, x, word: int) -> None:
-        """Key columns (parent id, x) and the zeroed presence ring, once the first pane shows x's type."""
+    def build(self, xs: List, word: int, sums=(-1, -1)) -> None:
+        """Key columns (parent id, x[, …]) and the zeroed presence ring, once the first pane shows the types."""
         o = self.owner
-        kind = 2 if isinstance(x, StrColumn) else 1 if x.data.dtype == torch.float64 else 0
+        kinds = [(x.dtype, 2 if isinstance(x, StrColumn) else 1 if x.data.dtype == torch.float64 else 0) for x in xs]
         self.word = word
-        self.keys, self.dictcols = o._alloc_keys([("long", 0), (x.dtype, kind)], self.pcap)
+        self.isum, self.fsum = sums
+        self.keys, self.dictcols = o._alloc_keys([("long", 0), *kinds], self.pcap)
         self.pres = torch.zeros((o.R + o.NB, self.pitch), dtype=torch.uint8, device=o.device)
 
-    def insert(self, gid: torch.Tensor, n: int, x, slot_idx: int, st) -> None:
+    def insert(self, gid: torch.Tensor, n: int, xs: List, slot_idx: int, st) -> None:
         """The pane's rows into the pair dictionary (the group insert kernel, with the rows' group ids as key
-        column 0) and the pairs they drew into presence row ``slot_idx``."""
+        column 0) and the pairs they drew into presence row ``slot_idx``.  A row with a NULL in any of ``xs`` creates
+        no pair: the validities are ANDed once."""
         o = self.owner
         dev = o.device
         gid64 = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         keep = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
         pid = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        v = N.u8(x.valid)
+        v = xs[0].valid
+        for x in xs[1:]:
+            if x.valid is not None:
+                v = x.valid.to(torch.bool) if v is None else v.to(torch.bool) & x.valid.to(torch.bool)
+        v = N.u8(v)
         if v is not None:
             v = v.contiguous()
         N.call("dxa_win_pair_prep", N.ptr(gid), n, o.gcap, N.ptr(v), N.ptr(gid64), N.ptr(keep), st)
-        kc = key_cols([PrimColumn("long", gid64), x])
+        kc = key_cols([PrimColumn("long", gid64), *xs])
         if kc is None:
             raise Ineligible("argument columns")
-        kc.ncols, kc.n = 2, n
+        kc.ncols, kc.n = 1 + len(xs), n
         N.call("dxa_win_insert_fused", ctypes.addressof(kc), ctypes.addressof(self.dictcols), N.ptr(keep),
                N.ptr(self.htab), self.hcap, N.ptr(self.gid_of_slot), self.scal_ptr, N.ptr(pid), st)
         N.call("dxa_win_pair_mark", N.ptr(pid), n, self.pcap, N.ptr(self.pres), self.pitch, slot_idx, st)
@@ -896,8 +987,8 @@ class DenseWindow:
         self._pinned = torch.empty((self.NB + 2, self.R), dtype=torch.int32, pin_memory=True)
         dkeys = []
         for _, func, arg in reqs:
-            if func == "dcount" and arg.key() not in dkeys:
-                dkeys.append(arg.key())
+            if func in _DISTINCT and distinct_key(arg) not in dkeys:
+                dkeys.append(distinct_key(arg))
         nstat = 4 + 4 * len(dkeys)      # the outer status, then counter / flags / 2 pads per pair state
         self._scal_pin = [torch.empty(nstat, dtype=torch.int32, pin_memory=True) for _ in range(2)]
         self._scal_k = 0
@@ -909,7 +1000,7 @@ class DenseWindow:
         self.gid_of_slot = torch.empty(cap, dtype=torch.int32, device=dev)
         self.scal = torch.zeros(nstat, dtype=torch.int32, device=dev)     # groups, bad flags, kept, pad[, pair states]
         N.call("dxa_win_init", N.ptr(self.htab), N.ptr(self.gid_of_slot), cap, N.stream_handle(dev))
-        # one pair state per different COUNT(DISTINCT x) argument, in order of first appearance
+        # one pair state per different distinct argument (or argument tuple), in order of first appearance
         self.pairs: List[PairState] = [PairState(self, k, dk) for k, dk in enumerate(dkeys)]
         self.keys = None                # dictionary key columns, built with the layout
         self.ring = None
@@ -962,7 +1053,12 @@ class DenseWindow:
             self.keys, self.dictcols = self._alloc_keys(kinds, self.gcap)
         except torch.cuda.OutOfMemoryError:
             raise Ineligible("memory") from None
-        L = plan_layout(self.reqs, {k: (c.dtype, c.data.dtype == torch.float64) for k, c in args.items()})
+        types = {k: (c.dtype, c.data.dtype == torch.float64) for k, c in args.items()}
+        for _, func, arg in self.reqs:
+            if func in ("dsum", "davg"):        # the distinct sums' arguments, as ``_distinct_arg`` widened them
+                c = dargs[arg.key()][0]
+                types.setdefault(arg.key(), (c.dtype, isinstance(c, PrimColumn) and c.data.dtype == torch.float64))
+        L = plan_layout(self.reqs, types)
         L["pspec_of"] = self._partial_spec
         # payload arguments stored as float32: their picks are kept as doubles and narrowed again in ``_finals``
         self.f32_args = {k for k, c in args.items() if c.data.dtype == torch.float32}
@@ -996,7 +1092,8 @@ class DenseWindow:
         try:
             self.ring, self.acc, self.keep, self.out_idx = self._alloc_ring(self.gcap)
             for ps in self.pairs:
-                ps.build(dargs[ps.arg_key], L["dcount_word"][ps.arg_key])
+                ps.build(dargs[ps.arg_key], L["dcount_word"][ps.arg_key],
+                         L.get("dsum_words", {}).get(ps.arg_key, (-1, -1)))
         except torch.cuda.OutOfMemoryError:
             self.layout = None
             raise Ineligible("memory") from None
@@ -1117,9 +1214,10 @@ class DenseWindow:
             keys = [PrimColumn("long", torch.zeros(n, dtype=torch.int64, device=self.device))]
         args, dargs = {}, {}
         for _, func, arg in self.reqs:
-            if func == "dcount":
-                if arg.key() not in dargs:
-                    dargs[arg.key()] = _distinct_arg(evaluate(arg, scope, ctx))
+            if func in _DISTINCT:
+                if distinct_key(arg) not in dargs:
+                    dargs[distinct_key(arg)] = [_distinct_arg(evaluate(a, scope, ctx))
+                                                for a in (arg if isinstance(arg, tuple) else (arg,))]
                 continue
             for a in arg if isinstance(arg, tuple) else () if arg is None else (arg,):
                 if a.key() in args:
@@ -1157,10 +1255,9 @@ class DenseWindow:
                 if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
                     raise Ineligible("key types changed")
             for ps in self.pairs:
-                dt, kind = ps.keys[1][:2]
-                k = dargs[ps.arg_key]
-                if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
-                    raise Ineligible("argument types changed")
+                for (dt, kind, *_), k in zip(ps.keys[1:], dargs[ps.arg_key]):
+                    if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
+                        raise Ineligible("argument types changed")
         L = self.layout
         dev = self.device
         st = N.stream_handle(dev)
@@ -1342,7 +1439,7 @@ class DenseWindow:
             folds = _PairFolds()
             for k, ps in enumerate(self.pairs):
                 folds.p[k] = _PairFold(ps.pres.data_ptr(), ps.pitch, ps.keys[0][2].data_ptr(), ps.scal_ptr, ps.pcap,
-                                       ps.word)
+                                       ps.word, ps.keys[1][2].data_ptr(), ps.keys[1][1], ps.isum, ps.fsum, 0)
             folds.n = len(self.pairs)
         # combine (the instantiation the layout's descriptors call for), folds, keep, compaction, output rows
         N.call("dxa_win_answer", N.ptr(self.ring), self.gcap, self.stride, N.ptr(slots_dev), len(slots),
@@ -1521,7 +1618,7 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
     from .expr import Scope
     store = t.store
     dev = t._device
-    distinct = any(c.distinct for c in aggs.values())
+    distinct = any(c.distinct or c.name == "approx_count_distinct" for c in aggs.values())
     if dev.type != "cuda" or (partial_proto is None and P.active() and t.dist != P.REPLICATED):
         return None
     if not sel.group_by and not distinct:   # a global statement without a distinct count keeps the paned path
@@ -1540,7 +1637,8 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
         if state is None:
             iv = max(1, store.interval_us)
             panes = store.conf.max_window_us // iv + store.conf.watermark_us // iv + 4
-            state = states[fp] = DenseWindow(dev, _requests(aggs, picks=True), max(panes, len(pieces) + 2),
+            state = states[fp] = DenseWindow(dev, _requests(aggs, picks=True, distinct_sums=True),
+                                             max(panes, len(pieces) + 2),
                                              global_form=not sel.group_by)
         state._rebuilt = set()
         proto = pieces[0][0].table

@@ -24,7 +24,11 @@
 // dxa_win_rehash below; the policy is the host's, dxa/engine/window_dense.py DenseWindow.rebuild).
 // COUNT(DISTINCT x) rides on the same ring: a pair dictionary keyed by (group id, x) and one presence byte per ring
 // slot and pair (win_pair_mark), ORed over the window and added into the combined rows between steps 3 and 4
-// (win_distinct_fold) — see the section before the entry points.
+// (win_distinct_fold) — see the section before the entry points.  The rest of the DISTINCT family is answered from the
+// same state: the pair dictionary holds every live pair's x, so SUM / AVG(DISTINCT x) are one more instantiation of
+// the fold, which also adds the live pairs' values into sum words of the combined row (reduced in the wave, one atomic
+// per parent, word and wave); count(DISTINCT a, b, …) is the count fold over a dictionary keyed by (group id, a, b, …)
+// — the same insert kernel with more key columns; approx_count_distinct is the exact distinct count.
 // The variance family (M2) and skewness / kurtosis / corr / covar (M3, M4, Cxy) keep centred sums per pane and group:
 // second passes over the pane fill them (win_m2_kernel, win_mom_kernel) and win_combine merges slots by the multi-way
 // form of Chan's update.
@@ -1023,7 +1027,8 @@ __global__ __launch_bounds__(256) void win_rehash_kernel(const DictCols d, uint6
 // over the window's panes.  Each distinct argument has a second persistent dictionary keyed by (parent group id, x)
 // — filled by win_insert_kernel itself, with the outer insert's ids widened to int64 as key column 0 — and a
 // presence ring of one byte per (ring slot, pair).  Bytes, not accumulator lines: at 2^20 pairs and ~320 slots the
-// presence ring is ~335 MB where 64-byte lines would be over 20 GB.
+// presence ring is ~335 MB where 64-byte lines would be over 20 GB.  count(DISTINCT a, b, …) has the key (parent
+// group id, a, b, …); SUM / AVG(DISTINCT x) read x back from key column 1 of x's dictionary (PairFold::vals).
 
 constexpr int kMaxPairStates = 4;
 struct PairFold {
@@ -1033,6 +1038,15 @@ struct PairFold {
   const int32_t* pscal;    // the pair dictionary's counter and flags
   int32_t pcap;
   int32_t word;            // the count word of the combined row this distinct count is added into
+  // SUM / AVG(DISTINCT x): the pair dictionary's key column 1 — every pair's x, int64 or the normalised bits of a
+  // double (``vkind`` KC_I64 / KC_F64) — and the words of the combined row the live pairs' values are added into: an
+  // MA_ADD_U64 word (the wrapping int64 sum) and an MA_ADD_F64 word (the sum as doubles); -1: absent.  Both absent
+  // (a distinct count alone): ``vals`` is not read
+  const int64_t* vals;
+  int32_t vkind;
+  int32_t isum;
+  int32_t fsum;
+  int32_t pad;
 };
 struct PairFolds {
   PairFold p[kMaxPairStates];
@@ -1083,6 +1097,14 @@ __global__ __launch_bounds__(256) void win_pair_or_kernel(const uint8_t* __restr
 // load per slot).  The adds are aggregated in the wave first — one atomic of the popcount per distinct parent per
 // wave and pair position: the global form has every pair under one parent, and every adder on one row runs an order
 // of magnitude below the float-atomic rate.  Counts are integers in f64, so the sums are exact in any order.
+// kSums (SUM / AVG(DISTINCT x); a layout without them runs the other instantiation, which is the kernel as it was):
+// a live pair's lane also loads the pair's x from the dictionary's value column — never for a pair that is not live —
+// and, in the same leader loop, the values of the parent's members are reduced over the wave (the other lanes
+// contribute 0 to a full-wave xor tree), so the leader issues one atomic per word beside the count's: an unsigned
+// 64-bit add into the integer word (wrapping, order-free) and an f64 add into the double word (the sum's last bits
+// depend on the arrival order, as every f64 atomic sum's do).  Values come from the dictionary: -0.0 is stored as
+// 0.0 and every NaN as the canonical one.
+template <bool kSums>
 __global__ __launch_bounds__(256) void win_distinct_fold_kernel(const PairFold f, const int32_t* __restrict__ slots,
                                                                 int32_t nslots, const int32_t* __restrict__ scal,
                                                                 int32_t gcap, double* __restrict__ acc,
@@ -1109,12 +1131,38 @@ __global__ __launch_bounds__(256) void win_distinct_fold_kernel(const PairFold f
       const int64_t par = on ? f.parent[p0 + q] : -1;
       const bool active = on && par >= 0 && par < ng;
       const int32_t mine = active ? (int32_t)par : -1;
+      unsigned long long xi = 0ull;
+      double xd = 0.0;
+      if (kSums && active) {
+        const int64_t b = f.vals[p0 + q];
+        xi = (unsigned long long)b;
+        xd = f.vkind == KC_F64 ? __longlong_as_double(b) : (double)b;
+      }
       unsigned long long todo = __ballot(active);
       while (todo) {
         const int lead = __ffsll((long long)todo) - 1;
         const int32_t first = __shfl(mine, lead);
-        const unsigned long long same = __ballot(active && mine == first);
-        if (lane == lead) atomicAdd(acc + (int64_t)first * stride + f.word, (double)__popcll(same));
+        const bool member = active && mine == first;
+        const unsigned long long same = __ballot(member);
+        double* row = acc + (int64_t)first * stride;
+        if (lane == lead) atomicAdd(row + f.word, (double)__popcll(same));
+        if (kSums) {
+          // (a parent with one member in this ballot — the usual case with many groups — needs no tree: ``same`` is
+          // wave-uniform, so is the branch)
+          const bool alone = (same & (same - 1)) == 0ull;
+          if (f.isum >= 0) {
+            unsigned long long si = member ? xi : 0ull;
+            if (!alone)
+              for (int o = 32; o; o >>= 1) si += __shfl_xor(si, o);
+            if (lane == lead) atomicAdd((unsigned long long*)row + f.isum, si);
+          }
+          if (f.fsum >= 0) {
+            double sd = member ? xd : 0.0;
+            if (!alone)
+              for (int o = 32; o; o >>= 1) sd += __shfl_xor(sd, o);
+            if (lane == lead) atomicAdd(row + f.fsum, sd);
+          }
+        }
         todo &= ~same;
       }
     }
@@ -1200,6 +1248,8 @@ static bool folds_ok(const PairFolds* pf, int32_t stride) {
   for (int k = 0; k < pf->n; ++k) {
     const PairFold& f = pf->p[k];
     if (f.word < 0 || f.word >= stride || (f.pitch & 15) || f.pitch < (int64_t)f.pcap + 1) return false;
+    if (f.isum < -1 || f.isum >= stride || f.fsum < -1 || f.fsum >= stride) return false;
+    if ((f.isum >= 0 || f.fsum >= 0) && (!f.vals || (f.vkind != KC_I64 && f.vkind != KC_F64))) return false;
   }
   return true;
 }
@@ -1276,9 +1326,12 @@ DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const
   hipMemsetAsync(scal + 2, 0, 4, s);
   launch_combine<false>((const unsigned long long*)ring, gcap, stride, slots, nslots, line_op, scal,
                         (unsigned long long*)acc, m2desc, momdesc, lodesc, pickdesc, s);
-  for (int k = 0; pf && k < pf->n; ++k)
-    hipLaunchKernelGGL(win_distinct_fold_kernel, dim3(dxa_blocks(((int64_t)pf->p[k].pcap + 15) >> 4, 256, 256 * 8)),
-                       dim3(256), 0, s, pf->p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  for (int k = 0; pf && k < pf->n; ++k) {
+    auto fold = pf->p[k].isum >= 0 || pf->p[k].fsum >= 0 ? win_distinct_fold_kernel<true>
+                                                         : win_distinct_fold_kernel<false>;
+    hipLaunchKernelGGL(fold, dim3(dxa_blocks(((int64_t)pf->p[k].pcap + 15) >> 4, 256, 256 * 8)), dim3(256), 0, s,
+                       pf->p[k], slots, nslots, scal, gcap, (double*)acc, stride);
+  }
   hipLaunchKernelGGL(win_keep_kernel, dim3(dxa_blocks(gcap, 256)), dim3(256), 0, s,
                      (const unsigned long long*)acc, stride, count_word, scal, gcap, keep, scal);
   hipLaunchKernelGGL(win_compact_kernel, dim3(1), dim3(256), 0, s, keep, gcap, scal, out_idx);
