@@ -20,7 +20,7 @@ from dxa.engine.expr import EvalContext
 from dxa.engine.query import Catalog, run_sql
 from dxa.ops import groupby as G
 from tests import agg_oracle as O
-from tests.test_window_dense_churn import S, dense_states, new_store, set_caps
+from tests.window_dense_support import S, dense_states, new_store, set_caps
 
 NAN, INF = math.nan, math.inf
 I_MIN, I_MAX = O.INT64_MIN, O.INT64_MAX
@@ -517,7 +517,7 @@ def test_ring_values(gpu, monkeypatch, block):
     """win_insert / agg_multi_kernel into pane slots / win_combine<false> (and <true> for complete blocks with
     BLOCK = 2) / win_emit over NaN, ±inf, ±0.0, NULL-only and ±2**63 arguments; id 104 lives in one pane only."""
     set_caps(monkeypatch, 8192, 8192, block=block)
-    store = new_store()
+    store = new_store(6)
     seen = {}
 
     def each(b, q, win):
@@ -536,7 +536,7 @@ def test_ring_keys(gpu, monkeypatch):
     """The ring's dictionary (win_insert_kernel store_key / key_differs, win_emit's key columns) over a double key
     (norm_f64_bits), a string key up to the 48-byte slot, and a (long, string) pair, NULLs in all of them."""
     set_caps(monkeypatch, 8192, 8192)
-    store = new_store()
+    store = new_store(6)
     run_ring(ring_stream(), [(Q_DOUBLE, ["dk"]), (Q_STRING, ["sk"]), (Q_PAIR, ["id", "sk"])], gpu, store)
     dense = dense_states(store)
     assert len(dense) == 3
@@ -549,7 +549,7 @@ def test_ring_key_too_long(gpu, monkeypatch):
     leaves the dense path saying why, and that batch and every later one still equal the oracle (the paned path
     answers them)."""
     set_caps(monkeypatch, 8192, 8192)
-    store = new_store()
+    store = new_store(6)
     state = {}
 
     def each(b, q, win):
@@ -566,7 +566,7 @@ def test_ring_key_too_long(gpu, monkeypatch):
 def test_window_statements_cpu():
     """The same stream and statements through the CPU evaluator (the oracle of the older ring tests)."""
     run_ring(ring_stream(), [(Q_VALUES, ["id"]), (Q_DOUBLE, ["dk"]), (Q_STRING, ["sk"]), (Q_PAIR, ["id", "sk"]),
-                             (Q_LONGKEY, ["sk49"])], CPU, new_store())
+                             (Q_LONGKEY, ["sk49"])], CPU, new_store(6))
 
 
 @functools.lru_cache(maxsize=None)
@@ -592,7 +592,7 @@ def test_ring_compaction_carry(gpu, monkeypatch):
     (no rebuild: the group counter stays at 4500), and once batch 0 has left the window only every 17th of them has
     rows, on both sides of group 4096."""
     set_caps(monkeypatch, 8192, 8192)
-    store = new_store()
+    store = new_store(6)
     after = {}
 
     def each(b, q, win):

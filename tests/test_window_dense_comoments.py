@@ -18,10 +18,11 @@ import torch
 
 from dxa.engine.column import PrimColumn, Table, strings_from_pylist
 from dxa.engine.expr import EvalContext
-from dxa.engine.query import Catalog, run_sql
-from dxa.engine.windows import TimeWindowConf, WindowStore
+from tests.window_dense_support import (S, Comparison, aggs_of, answer, as_partitioned_world_of_one, assumed_types,
+                                        churn_stream, dense_states, layout_of, new_store, only_state, rows_of,
+                                        run_stream, set_caps, small_stream, stable_stream, steady_state_launches,
+                                        two_rows_per_id_stream)
 
-S = 1_000_000
 REL, ABS = 1e-9, 1e-12
 DIMLESS_ABS = 1e-9
 DIMLESS = ("cr", "sk", "ku", "kh")           # result columns of corr / skewness / kurtosis, by name
@@ -47,14 +48,7 @@ Q_INT = ("SELECT deviceId, COUNT(*) AS c, SUM(temp) AS s, MIN(temp) AS mn, MAX(t
          "FROM W GROUP BY deviceId")
 Q_SD = ("SELECT deviceId, COUNT(*) AS c, AVG(temp) AS av, STDDEV(temp) AS sd, VAR_POP(temp) AS vp FROM W "
         "GROUP BY deviceId")
-STABLE = 200
-SEEN = {"rel": 0.0, "abs": 0.0, "dimless": 0.0}
-
-
-# ---- helpers (copies of tests/test_window_dense_moments.py's, with a second numeric column ``hum``) -----------------
-def drifting_ids(rng, b, n):
-    """Batch ``b``'s drifting ids: uniform in [4b, 4b + 12)."""
-    return rng.integers(4 * b, 4 * b + 12, n)
+NEAR = Comparison("tolerant", rel=REL, abs_=ABS, dimless=DIMLESS, dimless_abs=DIMLESS_ABS)
 
 
 def batch(rng, t_us, ids, spread=S - 1, temp=None, temp_valid=None, hum_valid=None):
@@ -81,133 +75,7 @@ def batch(rng, t_us, ids, spread=S - 1, temp=None, temp_valid=None, hum_valid=No
                   PrimColumn("double", torch.tensor(hv, dtype=torch.float64), torch.tensor(hvalid))], n, "cpu")
 
 
-def churn_stream(nb, spread=S - 1):
-    """200 rows per batch over the drifting ids → [(batch time, CPU table, ids)]."""
-    import numpy as np
-    rng = np.random.default_rng(23)
-    out = []
-    for b in range(nb):
-        ids = drifting_ids(rng, b, 200)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
-    return out
-
-
-def stable_stream(nb, drift, spread=S - 1):
-    """300 rows per batch: 200 over the stable ids and 100 over the drifting ids (or all 300 stable)."""
-    import numpy as np
-    rng = np.random.default_rng(29)
-    out = []
-    for b in range(nb):
-        ids = rng.integers(1000, 1000 + STABLE, 300)
-        if drift:
-            ids[200:] = drifting_ids(rng, b, 100)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
-    return out
-
-
-def rows_of(t):
-    """The table's rows as dicts of Python values (NULL as None), in a canonical order."""
-    t = t.to("cpu")
-    cols = {nm: t.column(nm).to_pylist() for nm in t.names}
-    rows = [{nm: cols[nm][i] for nm in t.names} for i in range(t.length)]
-    exact = [nm for nm in t.names if not any(isinstance(r[nm], float) for r in rows)]
-    return sorted(rows, key=lambda r: tuple(repr(r[nm]) for nm in exact))
-
-
-def oracle(q, view):
-    """The CPU evaluator's rows for statement ``q`` over the materialised window ``view``."""
-    mat = Table(view.names, view.columns, view.length, view._device)
-    cat = Catalog()
-    cat.register("W", mat.to("cpu"))
-    return rows_of(run_sql(q, cat, EvalContext(now_us=0)))
-
-
-def assert_rows(got, want, rel, abs_, dimless_abs, what):
-    """Keys, counts, NULLs and NaNs exactly; the columns named in ``DIMLESS`` within ``dimless_abs`` (no relative
-    test), other doubles within ``max(rel · |want|, abs_)``."""
-    assert len(got) == len(want), (what, len(got), len(want))
-    for g, w in zip(got, want):
-        assert g.keys() == w.keys(), what
-        for nm in w:
-            a, b = g[nm], w[nm]
-            if isinstance(a, float) and isinstance(b, float):
-                if math.isnan(a) or math.isnan(b):
-                    assert math.isnan(a) and math.isnan(b), (what, nm, g, w)
-                    continue
-                dev = abs(a - b)
-                if nm in DIMLESS:
-                    SEEN["dimless"] = max(SEEN["dimless"], dev)
-                    assert dev <= dimless_abs, (what, nm, a, b, g, w)
-                    continue
-                if dev > abs_:                      # (below the absolute tolerance a ratio says nothing)
-                    SEEN["rel"] = max(SEEN["rel"], dev / abs(b) if b else math.inf)
-                SEEN["abs"] = max(SEEN["abs"], dev)
-                assert dev <= max(rel * abs(b), abs_), (what, nm, a, b, g, w)
-            else:
-                assert type(a) is type(b) and a == b, (what, nm, g, w)
-
-
-def new_store(win=6):
-    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
-
-
-def dense_states(store):
-    return store.__dict__.get("_dense", {})
-
-
-def set_caps(monkeypatch, groups, groups_max, pairs, pairs_max, block=None):
-    from dxa.engine import window_dense
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS", groups)
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", groups_max)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS", pairs)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS_MAX", pairs_max)
-    if block is not None:
-        monkeypatch.setattr(window_dense, "BLOCK", block)
-
-
-def run_stream(stream, qs, dev, store, each=None, rel=REL, abs_=ABS, dimless_abs=DIMLESS_ABS, prepare=None):
-    """Every statement over every batch's window equals the CPU oracle; ``each(b, q, rows)`` after each."""
-    SEEN["rel"] = SEEN["abs"] = SEEN["dimless"] = 0.0
-    for b, (T, tbl, _ids) in enumerate(stream):
-        views, _ = store.process(tbl.to(dev), T, S)
-        if prepare is not None:
-            prepare(views["W"])
-        for q in qs:
-            cat = Catalog()
-            cat.register("W", views["W"])
-            rows = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
-            assert_rows(rows, oracle(q, views["W"]), rel, abs_, dimless_abs, (b, q))
-            if each is not None:
-                each(b, q, rows)
-    print(f"largest deviation from the oracle: relative {SEEN['rel']:.3e}, absolute {SEEN['abs']:.3e}, "
-          f"dimensionless (absolute) {SEEN['dimless']:.3e}")
-
-
-def only_state(store):
-    states = list(dense_states(store).values())
-    assert len(states) == 1
-    return states[0]
-
-
 # ---- CPU ------------------------------------------------------------------------------------------------------------
-def _aggs(*select_items):
-    from dxa.engine.query import _collect_aggs
-    from dxa.sql.parser import parse_select_item
-    aggs = {}
-    for item in select_items:
-        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
-    assert aggs
-    return aggs
-
-
-def _types(reqs, kind=("double", True)):
-    out = {}
-    for _, _f, arg in reqs:
-        for a in arg if isinstance(arg, tuple) else () if arg is None else (arg,):
-            out[a.key()] = kind
-    return out
-
-
 def test_layout_of_the_comoment_aggregates():
     """``_requests`` accepts the five names; skewness, STDDEV and AVG of one argument share its count, sum and M2
     words; corr / covar_pop / covar_samp of one (x, y) share the pair's words; the new words sit in the one op-4
@@ -216,12 +84,12 @@ def test_layout_of_the_comoment_aggregates():
     from dxa.engine.window_dense import MAX_VARIANCE, Ineligible, _requests, pair_keys, plan_layout
     from dxa.ops.groupby import (_F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP, _F_F64, _F_KURT, _F_SKEW, _F_SQRT,
                                  _F_VAR_SAMP, _MA_ADD_F64, _MA_M2, _MA_MOM, _MOM_CXY, _MOM_M3, _MOM_M4)
-    aggs = _aggs("COUNT(*)", "AVG(temp)", "STDDEV(temp)", "skewness(temp)", "kurtosis(temp)", "corr(temp, hum)",
+    aggs = aggs_of("COUNT(*)", "AVG(temp)", "STDDEV(temp)", "skewness(temp)", "kurtosis(temp)", "corr(temp, hum)",
                  "covar_pop(temp, hum)", "covar_samp(temp, hum)", "skewness(hum)")
     reqs = _requests(aggs)
     assert [f for _, f, _ in reqs] == ["count_star", "avg", "stddev", "skewness", "kurtosis", "corr", "covar_pop",
                                        "covar_samp", "skewness"]
-    L = plan_layout(reqs, _types(reqs))
+    L = plan_layout(reqs, assumed_types(reqs))
     by_func = {}
     for j, (_, f, _a) in enumerate(reqs):
         by_func.setdefault(f, L["fin"][j])
@@ -271,8 +139,8 @@ def test_layout_of_the_comoment_aggregates():
     assert pby["corr"] == dict(pby["covar_pop"], m2x=(_F_F64, word[("m2", px)], pc),
                                m2y=(_F_F64, word[("m2", py)], pc))
     # a statement without a new aggregate keeps today's layout, word for word
-    old = _requests(_aggs("COUNT(*)", "AVG(temp)", "STDDEV(temp)"))
-    Lo = plan_layout(old, _types(old))
+    old = _requests(aggs_of("COUNT(*)", "AVG(temp)", "STDDEV(temp)"))
+    Lo = plan_layout(old, assumed_types(old))
     assert Lo["line_ops"] == [_MA_ADD_F64, _MA_M2] and Lo["stride"] == 16
     assert Lo["fin"] == [(0, 0, -1), (3, 2, 1), (_F_VAR_SAMP | _F_SQRT, 8, 1)]
     assert Lo["m2desc"] == [0] * 8 + [1 | 2 << 16] + [0] * 7
@@ -281,20 +149,20 @@ def test_layout_of_the_comoment_aggregates():
     for bad in ("corr(DISTINCT temp, hum)", "skewness(DISTINCT temp)", "kurtosis(DISTINCT temp)",
                 "covar_pop(DISTINCT temp, hum)", "covar_samp(DISTINCT temp, hum)", "corr(temp)", "skewness(temp, hum)"):
         with pytest.raises(Ineligible):
-            _requests(_aggs(bad))
+            _requests(aggs_of(bad))
     for bad in ("skewness(ok)", "kurtosis(ok)", "corr(ok, temp)", "covar_pop(temp, ok)", "covar_samp(ok, ok)"):
-        r = _requests(_aggs(bad))
+        r = _requests(aggs_of(bad))
         with pytest.raises(Ineligible):
-            plan_layout(r, _types(r, ("boolean", False)))
+            plan_layout(r, assumed_types(r, ("boolean", False)))
     # the new cap has a reason of its own; the variance cap keeps its own
-    _requests(_aggs(*[f"covar_pop(x{i}, y)" for i in range(8)]))
+    _requests(aggs_of(*[f"covar_pop(x{i}, y)" for i in range(8)]))
     with pytest.raises(Ineligible, match="too many moment arguments"):
-        _requests(_aggs(*[f"covar_pop(x{i}, y)" for i in range(9)]))
+        _requests(aggs_of(*[f"covar_pop(x{i}, y)" for i in range(9)]))
     with pytest.raises(Ineligible, match="too many moment arguments"):
-        _requests(_aggs(*[f"skewness(x{i})" for i in range(9)]))
+        _requests(aggs_of(*[f"skewness(x{i})" for i in range(9)]))
     assert MAX_VARIANCE == 8
     with pytest.raises(Ineligible, match="too many variance arguments"):
-        _requests(_aggs(*[f"STDDEV(x{i})" for i in range(9)]))
+        _requests(aggs_of(*[f"STDDEV(x{i})" for i in range(9)]))
 
 
 def _call_text(name):
@@ -310,9 +178,9 @@ def test_partial_states_are_those_of_local_partials():
     prototype), so ``_partial_spec`` finds a word for every partial column and carries no other.  COUNT(DISTINCT x)
     is not decomposable and has no entry in ``pfin`` at all."""
     from dxa.engine import distagg as D
-    from dxa.engine.column import ConstColumn, materialize
+    from dxa.engine.column import materialize
     from dxa.engine.expr import Scope, evaluate
-    from dxa.engine.window_dense import _SUPPORTED, _requests, plan_layout
+    from dxa.engine.window_dense import _SUPPORTED
     from dxa.sql.parser import parse_select_item
     import numpy as np
     empty = batch(np.random.default_rng(0), 100 * S, np.arange(4)).take(torch.empty(0, dtype=torch.int64))
@@ -322,17 +190,10 @@ def test_partial_states_are_those_of_local_partials():
     keys = [materialize(evaluate(g, scope, ctx)) for g in gx]
 
     def layout(aggs):
-        reqs = _requests(aggs)
-        types = {}
-        for _, f, arg in reqs:
-            for a in arg if isinstance(arg, tuple) else () if arg is None or f == "dcount" else (arg,):
-                c = evaluate(a, scope, ctx)
-                c = c.materialize() if isinstance(c, ConstColumn) else c
-                types[a.key()] = (c.dtype, c.data.dtype == torch.float64)
-        return plan_layout(reqs, types)
+        return layout_of(aggs, empty)[2]
 
     for text in ["COUNT(*)"] + [_call_text(name) for name in sorted(_SUPPORTED)]:
-        aggs = _aggs(text)
+        aggs = aggs_of(text)
         (ak,) = aggs
         assert D.decomposable(aggs, ctx), text
         _partial, plan, _key_names = D.local_partials(gx, keys, aggs, scope, ctx)
@@ -340,7 +201,7 @@ def test_partial_states_are_those_of_local_partials():
         assert len(set(suffixes)) == len(suffixes) > 0, text
         assert set(layout(aggs)["pfin"][ak]) == set(suffixes), (text, suffixes)
     for text in ("COUNT(DISTINCT temp)", "COUNT(DISTINCT kind)"):
-        aggs = _aggs("AVG(temp)", text)
+        aggs = aggs_of("AVG(temp)", text)
         avg, dc = aggs
         assert not D.decomposable(aggs, ctx) and aggs[dc].distinct
         L = layout(aggs)
@@ -375,9 +236,9 @@ def test_partials_merge_to_the_whole(nsub):
     from dxa.sql.parser import parse_select_item
     whole = _whole_table()
     ctx = EvalContext(now_us=0)
-    aggs = _aggs(*_WHOLE_ITEMS)
+    aggs = aggs_of(*_WHOLE_ITEMS)
     assert D.decomposable(aggs, ctx)
-    assert all(D.decomposable(_aggs(one), ctx) for one in ("corr(a, b)", "covar_pop(a, b)", "covar_samp(a, b)",
+    assert all(D.decomposable(aggs_of(one), ctx) for one in ("corr(a, b)", "covar_pop(a, b)", "covar_samp(a, b)",
                                                            "skewness(a)", "kurtosis(a)"))
     gx = [parse_select_item("deviceId").expr]
     # subsets by row index: [0], the rest dealt round-robin (rows 1 and 2 of id 77 land elsewhere), and an empty one
@@ -407,25 +268,22 @@ def test_partials_merge_to_the_whole(nsub):
     for nm, ak in zip(_WHOLE_NAMES, aggs):
         cols[nm] = finals[ak].to_pylist()
     rows = sorted(({nm: v[i] for nm, v in cols.items()} for i in range(ng)), key=lambda r: r["deviceId"])
-    cat = Catalog()
-    cat.register("W", whole)
-    want = sorted(rows_of(run_sql(Q_WHOLE, cat, ctx)), key=lambda r: r["deviceId"])
-    SEEN["rel"] = SEEN["abs"] = SEEN["dimless"] = 0.0
-    assert_rows(rows, want, REL, ABS, DIMLESS_ABS, nsub)
-    print(f"largest deviation: relative {SEEN['rel']:.3e}, absolute {SEEN['abs']:.3e}, "
-          f"dimensionless {SEEN['dimless']:.3e}")
+    NEAR.reset()
+    NEAR((rows, None), rows_of(answer(Q_WHOLE, whole, ctx=ctx), order_by="deviceId"), nsub)
+    NEAR.report()
 
 
 def test_cpu_stream_takes_the_pane_partials():
     """On a CPU device the statements are answered from pane partials (no dense state is created) and equal the
     oracle; the window in which nothing passes the WHERE gives counts 0 and NULLs."""
-    store = new_store()
+    store = new_store(6)
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         if q == Q_DNONE:
             assert rows == [{"dd": 0, "cr": None, "cs": None, "sk": None, "ci": 0}]
 
-    run_stream(churn_stream(8), [Q_ALL, Q_FIVE, Q_DGLOB, Q_DNONE, Q_MOD], torch.device("cpu"), store, each)
+    run_stream(churn_stream(batch, 8), [Q_ALL, Q_FIVE, Q_DGLOB, Q_DNONE, Q_MOD], torch.device("cpu"), store, NEAR,
+               each)
     assert not dense_states(store)
 
 
@@ -439,15 +297,15 @@ def test_all_five_in_one_statement(gpu, monkeypatch, block, spread):
     scratch slots.  Before these aggregates were decomposable the statement had no dense state at all."""
     from dxa.engine import window_dense
     monkeypatch.setattr(window_dense, "BLOCK", block)
-    store = new_store(win=8)
+    store = new_store(8)
     seen = {"blocks": 0}
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         for d in dense_states(store).values():
             if not d.disabled:
                 seen["blocks"] = max(seen["blocks"], len(d.blocks))
 
-    run_stream(stable_stream(24, True, spread), [Q_ALL], gpu, store, each)
+    run_stream(stable_stream(batch, 24, True, spread=spread), [Q_ALL], gpu, store, NEAR, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert 4 in d.layout["line_ops"] and 3 in d.layout["line_ops"] and len(d.pairs) == 1
@@ -476,11 +334,11 @@ def _edge_stream(nb):
 
 @pytest.mark.gpu
 def test_edge_groups(gpu):
-    store = new_store()
+    store = new_store(6)
     nb = 14
     counts = {"one": 0, "null": 0, "apart": 0, "const": 0}
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         for r in rows:
             i = r["deviceId"]
             if i >= 9000:
@@ -500,7 +358,7 @@ def test_edge_groups(gpu):
                 assert all(math.isnan(r[k]) for k in ("cs", "cr", "sk", "ku")), r
                 counts["one"] += 1
 
-    run_stream(_edge_stream(nb), [Q_EDGE], gpu, store, each)
+    run_stream(_edge_stream(nb), [Q_EDGE], gpu, store, NEAR, each)
     assert not only_state(store).disabled
     assert all(v > nb for v in counts.values()), counts
 
@@ -511,8 +369,9 @@ def test_offset_values(gpu, monkeypatch):
     1e-6 (raw power sums would lose every digit)."""
     from dxa.engine import window_dense
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store()
-    run_stream(stable_stream(14, False), [Q_OFFSET], gpu, store, rel=1e-6, dimless_abs=1e-6)
+    store = new_store(6)
+    run_stream(stable_stream(batch, 14, False), [Q_OFFSET], gpu, store,
+               Comparison("tolerant", rel=1e-6, abs_=ABS, dimless=DIMLESS, dimless_abs=1e-6))
     d = only_state(store)
     assert not d.disabled and 4 in d.layout["line_ops"]
 
@@ -522,8 +381,8 @@ def test_rebuild_moves_op4_lines(gpu, monkeypatch):
     """Ids drift through a 16-id dictionary that grows to 64 at most: every rebuild renumbers the op-4 line with the
     others, and the 2-pane blocks are combined again afterwards."""
     set_caps(monkeypatch, 16, 64, 1 << 16, 1 << 20, block=2)
-    store = new_store()
-    run_stream(churn_stream(40), [Q_FIVE], gpu, store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 40), [Q_FIVE], gpu, store, NEAR)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert d.rebuilds > 0 and d.gcap <= 64 and 4 in d.layout["line_ops"]
@@ -535,19 +394,12 @@ def test_straddles_the_lds_bound(gpu, monkeypatch):
     a second statement whose three groups are all privatised."""
     from dxa.engine import window_dense
     from dxa.ops import native as N
-    import numpy as np
     L = N.lib().dxa_win_m2_lds_groups()
     assert L > 0
     if L + 200 > window_dense.DENSE_GROUPS:
         monkeypatch.setattr(window_dense, "DENSE_GROUPS", 2 * (L + 200))
-    rng = np.random.default_rng(37)
-    stream = []
-    for b in range(9):
-        ids = np.repeat(np.arange(L + 200), 2)
-        rng.shuffle(ids)
-        stream.append(((100 + b) * S, batch(rng, (100 + b) * S, ids), ids))
-    store = new_store()
-    run_stream(stream, [Q_FIVE, Q_MOD], gpu, store)
+    store = new_store(6)
+    run_stream(two_rows_per_id_stream(batch, 9, L + 200), [Q_FIVE, Q_MOD], gpu, store, NEAR)
     states = list(dense_states(store).values())
     assert len(states) == 2 and not any(d.disabled for d in states)
     assert all(4 in d.layout["line_ops"] for d in states)
@@ -557,13 +409,13 @@ def test_straddles_the_lds_bound(gpu, monkeypatch):
 def test_global_form_with_count_distinct(gpu):
     """No GROUP BY: corr / covar_samp / skewness beside COUNT(DISTINCT deviceId), and the window in which nothing
     passes the WHERE (counts 0, the rest NULL)."""
-    store = new_store()
+    store = new_store(6)
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         if q == Q_DNONE:
             assert rows == [{"dd": 0, "cr": None, "cs": None, "sk": None, "ci": 0}]
 
-    run_stream(churn_stream(12), [Q_DGLOB, Q_DNONE], gpu, store, each)
+    run_stream(churn_stream(batch, 12), [Q_DGLOB, Q_DNONE], gpu, store, NEAR, each)
     states = list(dense_states(store).values())
     assert len(states) == 2 and not any(d.disabled for d in states)
     assert all(len(d.pairs) == 1 and 4 in d.layout["line_ops"] for d in states)
@@ -571,28 +423,12 @@ def test_global_form_with_count_distinct(gpu):
 
 @pytest.mark.gpu
 def test_partials_at_world_size_one(gpu, monkeypatch):
-    """The N-rank form at world size 1 (the patching of test_window_dense_moments.py::test_partials): the ring hands
+    """The N-rank form at world size 1 (``as_partitioned_world_of_one``): the ring hands
     ``merge_partials`` the states of ``distagg._partials``."""
-    from dxa import parallel as P
-    from dxa.engine import distagg, window_dense
-    monkeypatch.setattr(P, "active", lambda: True)
-    monkeypatch.setattr(distagg, "exchange_partials", lambda partial, key_names, grouped: (partial, P.HASHED))
-    calls = {"n": 0}
-    real = window_dense.dense_partials
-
-    def counted(*a, **k):
-        got = real(*a, **k)
-        calls["n"] += got is not None
-        return got
-
-    monkeypatch.setattr(window_dense, "dense_partials", counted)
-
-    def prepare(view):
-        view.dist = P.PARTITIONED
-
-    store = new_store()
-    stream = churn_stream(12)
-    run_stream(stream, [Q_FIVE], gpu, store, prepare=prepare)
+    calls, prepare = as_partitioned_world_of_one(monkeypatch)
+    store = new_store(6)
+    stream = churn_stream(batch, 12)
+    run_stream(stream, [Q_FIVE], gpu, store, NEAR, prepare=prepare)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert calls["n"] >= len(stream) - 4          # (the watermark keeps the first windows empty)
@@ -600,8 +436,8 @@ def test_partials_at_world_size_one(gpu, monkeypatch):
 
 @pytest.mark.gpu
 def test_plain_statements_have_no_op4_line(gpu):
-    store = new_store()
-    run_stream(churn_stream(12), [Q_INT, Q_SD], gpu, store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 12), [Q_INT, Q_SD], gpu, store, NEAR)
     states = list(dense_states(store).values())
     assert len(states) == 2 and not any(d.disabled for d in states)
     for d in states:
@@ -616,20 +452,6 @@ Q_SK = "SELECT deviceId, skewness(temp) AS sk FROM W GROUP BY deviceId"
 Q_DC = "SELECT deviceId, COUNT(*) AS c, COUNT(DISTINCT kind) AS dk FROM W GROUP BY deviceId"
 
 
-def small_stream(nb, mid_pane=False, groups=4, rows=40):
-    """40 rows per batch over 4 ids.  ``mid_pane``: event times in the middle half of the batch's second, so a pane is
-    wholly inside a window or wholly outside it (none is clipped into a scratch slot) and exactly one pane enters
-    the window per batch."""
-    import numpy as np
-    rng = np.random.default_rng(43)
-    out = []
-    for b in range(nb):
-        ids = rng.integers(0, groups, rows)
-        T = (100 + b) * S
-        out.append((T, batch(rng, T - S // 4, ids, S // 2) if mid_pane else batch(rng, T, ids), ids))
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("q", [Q_CP, Q_CP_GLOB])
 def test_covar_pop_alone(gpu, monkeypatch, q):
@@ -637,14 +459,14 @@ def test_covar_pop_alone(gpu, monkeypatch, q):
     2-pane block combine; grouped, and in global form beside COUNT(DISTINCT deviceId)."""
     from dxa.engine import window_dense
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store()
+    store = new_store(6)
     seen = {"blocks": 0}
 
-    def each(b, _q, rows):
+    def each(b, _q, rows, view, table):
         for d in dense_states(store).values():
             seen["blocks"] = max(seen["blocks"], len(d.blocks))
 
-    run_stream(small_stream(14), [q], gpu, store, each)
+    run_stream(small_stream(batch, 14), [q], gpu, store, NEAR, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert d.momdesc_dev is not None and d.m2desc_dev is not None and not any(d.layout["m2desc"])
@@ -661,28 +483,16 @@ def test_entry_points_per_steady_state_batch(gpu, monkeypatch, q, second_pass, p
     completes a 2-pane block — one block combine and one presence OR per pair state, then the one answer.  A layout
     without a family issues none of its launches."""
     from dxa.engine import window_dense
-    from launch_count import count_launches
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store()
+    store = new_store(6)
     pane = ["dxa_win_insert_fused", "dxa_aggregate_multi", *second_pass,
             *["dxa_win_pair_prep", "dxa_win_insert_fused", "dxa_win_pair_mark"] * pairs]
     block = ["dxa_win_combine_block", *["dxa_win_pair_or_block"] * pairs]
     completed_seen = set()
-    for b, (T, tbl, _ids) in enumerate(small_stream(14, mid_pane=True)):
-        views, _ = store.process(tbl.to(gpu), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        states = list(dense_states(store).values())
-        before = set(states[0].blocks) if states else set()
-        with count_launches() as log:
-            out = run_sql(q, cat, EvalContext(now_us=0, device=gpu))
-        assert_rows(rows_of(out), oracle(q, views["W"]), REL, ABS, DIMLESS_ABS, (b, q))
-        if b < 8:                                   # the watermark and the 6-pane window: full from batch 7 on
-            continue
+    # the watermark and the 6-pane window: full from batch 7 on
+    for b, native, completed in steady_state_launches(gpu, store, small_stream(batch, 14, mid_pane=True), q, NEAR, 8):
         d = only_state(store)
         assert not d.disabled and d.rebuilds == 0 and len(d.pairs) == pairs
-        completed = len(set(d.blocks) - before)
         completed_seen.add(completed)
-        native = [nm for nm in log if nm.startswith("dxa_")]
         assert native == pane + block * completed + ["dxa_win_answer"], (b, native)
     assert completed_seen == {0, 1}

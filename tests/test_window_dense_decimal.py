@@ -14,17 +14,16 @@ of 64 rows it is sum · 156.25, an exact half when the sum is 2 mod 4 (an odd su
 next to a tie).  The tie stream has groups of both sizes with odd sums of both signs and, for 64 rows, sums that
 are 2 mod 4 as well."""
 import decimal as pd
-import math
 
 import pytest
 import torch
 
 from dxa.engine.column import PrimColumn, Table, strings_from_pylist
 from dxa.engine.expr import EvalContext
-from dxa.engine.query import Catalog, run_sql
-from dxa.engine.windows import TimeWindowConf, WindowStore
+from tests.window_dense_support import (S, Comparison, aggs_of, as_partitioned_world_of_one, churn_stream,
+                                        dense_states, layout_of, new_store, only_state, run_stream, set_caps,
+                                        small_stream, stable_stream, steady_state_launches, two_rows_per_id_stream)
 
-S = 1_000_000
 REL, ABS = 1e-9, 1e-12
 DIMLESS_ABS = 1e-9
 DIMLESS = ("cr", "sk")
@@ -51,13 +50,7 @@ Q_MOD = (f"SELECT deviceId % 3 AS m, COUNT(*) AS c, SUM({WIDE}) AS sw, AVG({N18}
 Q_P30 = "SELECT deviceId, COUNT(*) AS c, SUM(CAST(temp AS DECIMAL(30,2))) AS s FROM W GROUP BY deviceId"
 Q_INT = ("SELECT deviceId, COUNT(*) AS c, SUM(temp) AS s, MIN(temp) AS mn, MAX(temp) AS mx, AVG(temp) AS av "
          "FROM W GROUP BY deviceId")
-SEEN = {"rel": 0.0, "abs": 0.0, "dimless": 0.0}
-
-
-# ---- helpers (copies of tests/test_window_dense_comoments.py's; ``temp`` is a long here) ----------------------------
-def drifting_ids(rng, b, n):
-    """Batch ``b``'s drifting ids: uniform in [4b, 4b + 12)."""
-    return rng.integers(4 * b, 4 * b + 12, n)
+TYPED = Comparison("tolerant", rel=REL, abs_=ABS, dimless=DIMLESS, dimless_abs=DIMLESS_ABS, types=True)
 
 
 def batch(rng, t_us, ids, spread=S - 1, temp=None, temp_valid=None, big=None, wide=None):
@@ -86,138 +79,6 @@ def batch(rng, t_us, ids, spread=S - 1, temp=None, temp_valid=None, big=None, wi
 def wide_text(u):
     """The text of the decimal with unscaled value ``u`` at scale 3."""
     return ("-" if u < 0 else "") + f"{abs(u) // 1000}.{abs(u) % 1000:03d}"
-
-
-def churn_stream(nb, spread=S - 1):
-    """200 rows per batch over the drifting ids → [(batch time, CPU table, ids)]."""
-    import numpy as np
-    rng = np.random.default_rng(23)
-    out = []
-    for b in range(nb):
-        ids = drifting_ids(rng, b, 200)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
-    return out
-
-
-def stable_stream(nb, spread=S - 1):
-    """300 rows per batch: 200 over 200 stable ids and 100 over the drifting ids."""
-    import numpy as np
-    rng = np.random.default_rng(29)
-    out = []
-    for b in range(nb):
-        ids = rng.integers(1000, 1200, 300)
-        ids[200:] = drifting_ids(rng, b, 100)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids, spread), ids))
-    return out
-
-
-def small_stream(nb, groups=4, rows=40):
-    """40 rows per batch over 4 ids, event times in the middle half of the batch's second: a pane is wholly inside a
-    window or wholly outside it, and exactly one pane enters the window per batch."""
-    import numpy as np
-    rng = np.random.default_rng(43)
-    out = []
-    for b in range(nb):
-        ids = rng.integers(0, groups, rows)
-        T = (100 + b) * S
-        out.append((T, batch(rng, T - S // 4, ids, S // 2), ids))
-    return out
-
-
-def rows_of(t):
-    """The table's rows as dicts of Python values (NULL as None), in a canonical order, and its column dtypes."""
-    t = t.to("cpu")
-    cols = {nm: t.column(nm).to_pylist() for nm in t.names}
-    rows = [{nm: cols[nm][i] for nm in t.names} for i in range(t.length)]
-    exact = [nm for nm in t.names if not any(isinstance(r[nm], float) for r in rows)]
-    return (sorted(rows, key=lambda r: tuple(repr(r[nm]) for nm in exact)),
-            {nm: str(t.column(nm).dtype) for nm in t.names})
-
-
-def oracle(q, view):
-    """The CPU evaluator's rows and dtypes for statement ``q`` over the materialised window ``view``."""
-    mat = Table(view.names, view.columns, view.length, view._device)
-    cat = Catalog()
-    cat.register("W", mat.to("cpu"))
-    return rows_of(run_sql(q, cat, EvalContext(now_us=0)))
-
-
-def assert_rows(got, want, what):
-    """Dtype strings, keys, counts, NULLs and decimals exactly (value and text); doubles as the moments tests."""
-    (got, gtypes), (want, wtypes) = got, want
-    assert gtypes == wtypes, (what, gtypes, wtypes)
-    assert len(got) == len(want), (what, len(got), len(want))
-    for g, w in zip(got, want):
-        assert g.keys() == w.keys(), what
-        for nm in w:
-            a, b = g[nm], w[nm]
-            if isinstance(a, float) and isinstance(b, float):
-                if math.isnan(a) or math.isnan(b):
-                    assert math.isnan(a) and math.isnan(b), (what, nm, g, w)
-                    continue
-                dev = abs(a - b)
-                if nm in DIMLESS:
-                    SEEN["dimless"] = max(SEEN["dimless"], dev)
-                    assert dev <= DIMLESS_ABS, (what, nm, a, b, g, w)
-                    continue
-                if dev > ABS:
-                    SEEN["rel"] = max(SEEN["rel"], dev / abs(b) if b else math.inf)
-                SEEN["abs"] = max(SEEN["abs"], dev)
-                assert dev <= max(REL * abs(b), ABS), (what, nm, a, b, g, w)
-            else:
-                assert type(a) is type(b) and a == b and str(a) == str(b), (what, nm, g, w)
-
-
-def new_store(win=6):
-    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
-
-
-def dense_states(store):
-    return store.__dict__.get("_dense", {})
-
-
-def set_caps(monkeypatch, groups, groups_max, pairs, pairs_max, block=None):
-    from dxa.engine import window_dense
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS", groups)
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", groups_max)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS", pairs)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS_MAX", pairs_max)
-    if block is not None:
-        monkeypatch.setattr(window_dense, "BLOCK", block)
-
-
-def run_stream(stream, qs, dev, store, each=None, prepare=None):
-    """Every statement over every batch's window equals the CPU oracle; ``each(b, q, rows)`` after each."""
-    SEEN["rel"] = SEEN["abs"] = SEEN["dimless"] = 0.0
-    for b, (T, tbl, _ids) in enumerate(stream):
-        views, _ = store.process(tbl.to(dev), T, S)
-        if prepare is not None:
-            prepare(views["W"])
-        for q in qs:
-            cat = Catalog()
-            cat.register("W", views["W"])
-            got = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
-            assert_rows(got, oracle(q, views["W"]), (b, q))
-            if each is not None:
-                each(b, q, got[0])
-    print(f"largest deviation of the doubles from the oracle: relative {SEEN['rel']:.3e}, absolute "
-          f"{SEEN['abs']:.3e}, dimensionless (absolute) {SEEN['dimless']:.3e}")
-
-
-def only_state(store):
-    states = list(dense_states(store).values())
-    assert len(states) == 1
-    return states[0]
-
-
-def _aggs(*select_items):
-    from dxa.engine.query import _collect_aggs
-    from dxa.sql.parser import parse_select_item
-    aggs = {}
-    for item in select_items:
-        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
-    assert aggs
-    return aggs
 
 
 # ---- the streams of the edge cases ----------------------------------------------------------------------------------
@@ -283,7 +144,7 @@ def ties_stream(nb):
 
 
 def tie_checker(seen):
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         if q != Q_TIES:
             return
         for r in rows:
@@ -320,10 +181,10 @@ def test_layout_of_the_decimal_aggregates():
     ``pfin`` has exactly the suffixes of ``distagg._partials``; SUM of decimal(30,2) is ineligible with a reason of
     its own; a layout without decimals has no decimal job and no ``lodesc``."""
     from dxa.engine import distagg as D
-    from dxa.engine.column import ConstColumn, materialize
+    from dxa.engine.column import materialize
     from dxa.engine.decimal import DecimalType
     from dxa.engine.expr import Scope, evaluate
-    from dxa.engine.window_dense import Ineligible, _requests, plan_layout
+    from dxa.engine.window_dense import Ineligible
     from dxa.ops.groupby import (_DEC_KEY_MAX, _DEC_KEY_MIN, _DEC_SUM, _F_COUNT, _F_DEC_AVG, _F_DEC_MM, _F_DEC_SUM,
                                  _F_HI, _F_I64, _F_NOT, _MA_ADD_F64, _MA_ADD_U64, _MA_LOKEY, _MA_MAX, _MV_I64, _MV_NOT)
     from dxa.sql.parser import parse_select_item
@@ -333,18 +194,11 @@ def test_layout_of_the_decimal_aggregates():
     scope = Scope.of_table(empty, "W")
 
     def layout(aggs):
-        reqs = _requests(aggs)
-        types = {}
-        for _, f, arg in reqs:
-            for a in arg if isinstance(arg, tuple) else () if arg is None or f == "dcount" else (arg,):
-                c = evaluate(a, scope, ctx)
-                c = c.materialize() if isinstance(c, ConstColumn) else c
-                types[a.key()] = (c.dtype, c.data.dtype == torch.float64)
-        return reqs, types, plan_layout(reqs, types)
+        return layout_of(aggs, empty)
 
     items = ["COUNT(*)", f"SUM({N18})", f"AVG({N18})", f"MIN({N18})", f"SUM({WIDE})", f"AVG({WIDE})", f"MIN({WIDE})",
              f"MAX({WIDE})", f"STDDEV({WIDE})", "AVG(hum)"]
-    aggs = _aggs(*items)
+    aggs = aggs_of(*items)
     reqs, types, L = layout(aggs)
     n18, wide = reqs[1][2].key(), reqs[4][2].key()
     assert types[n18] == (DecimalType(18, 2), False) and types[wide] == (DecimalType(24, 1), False)
@@ -405,12 +259,12 @@ def test_layout_of_the_decimal_aggregates():
     assert ("sumf", wide) in word and ("m2", wide) in word
     # more than 28 digits: Spark's sum type is capped, the total can overflow
     with pytest.raises(Ineligible, match="decimal precision"):
-        layout(_aggs("SUM(CAST(temp AS DECIMAL(30,2)))"))
+        layout(aggs_of("SUM(CAST(temp AS DECIMAL(30,2)))"))
     with pytest.raises(Ineligible, match="decimal precision"):
-        layout(_aggs("AVG(CAST(temp AS DECIMAL(29,2)))"))
-    layout(_aggs("SUM(CAST(temp AS DECIMAL(28,2)))", "MIN(CAST(temp AS DECIMAL(38,2)))"))
+        layout(aggs_of("AVG(CAST(temp AS DECIMAL(29,2)))"))
+    layout(aggs_of("SUM(CAST(temp AS DECIMAL(28,2)))", "MIN(CAST(temp AS DECIMAL(38,2)))"))
     # a statement without decimals keeps its layout and has no decimal job and no low-key descriptor
-    _r, _t, Lo = layout(_aggs("COUNT(*)", "SUM(temp)", "MIN(temp)", "AVG(hum)"))
+    _r, _t, Lo = layout(aggs_of("COUNT(*)", "SUM(temp)", "MIN(temp)", "AVG(hum)"))
     assert "decargs" not in Lo and "lodesc" not in Lo and _MA_LOKEY not in Lo["line_ops"]
     assert Lo["rows"] == [(j, 1) for j in range(4)] and Lo["fin"] == [(0, 8, -1), (1, 0, 9), (9, 16, 9), (3, 11, 10)]
 
@@ -418,11 +272,11 @@ def test_layout_of_the_decimal_aggregates():
 def test_cpu_stream_takes_the_pane_partials():
     """On a CPU device the decimal statements are answered from pane partials (no dense state is created) and equal
     the oracle — which guards the oracle and the streams: the tie groups are seen whole, with exact halves."""
-    store = new_store()
-    run_stream(stable_stream(8), [Q_ALL, Q_FAM], torch.device("cpu"), store)
-    run_stream(carry_stream(8), [Q_CARRY], torch.device("cpu"), new_store())
+    store = new_store(6)
+    run_stream(stable_stream(batch, 8), [Q_ALL, Q_FAM], torch.device("cpu"), store, TYPED)
+    run_stream(carry_stream(8), [Q_CARRY], torch.device("cpu"), new_store(6), TYPED)
     seen = {"null": 0, "one": 0, "tie": set()}
-    run_stream(ties_stream(12), [Q_TIES], torch.device("cpu"), new_store(), tie_checker(seen))
+    run_stream(ties_stream(12), [Q_TIES], torch.device("cpu"), new_store(6), TYPED, tie_checker(seen))
     assert seen["tie"] == {3201, 3202, 6401, 6402, 6403, 6404} and seen["null"] > 12 and seen["one"] > 6, seen
     assert not dense_states(store)
 
@@ -437,15 +291,15 @@ def test_all_decimal_aggregates_in_one_statement(gpu, monkeypatch, block):
     from dxa.engine import window_dense
     from dxa.ops.groupby import _MA_LOKEY
     monkeypatch.setattr(window_dense, "BLOCK", block)
-    store = new_store()
+    store = new_store(6)
     seen = {"blocks": 0}
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         for d in dense_states(store).values():
             if not d.disabled:
                 seen["blocks"] = max(seen["blocks"], len(d.blocks))
 
-    run_stream(stable_stream(14), [Q_ALL, Q_FAM], gpu, store, each)
+    run_stream(stable_stream(batch, 14), [Q_ALL, Q_FAM], gpu, store, TYPED, each)
     states = list(dense_states(store).values())
     assert len(states) == 2
     for d in states:
@@ -463,10 +317,10 @@ def test_carries_and_signs(gpu, monkeypatch):
     2-pane blocks, so both combines apply the "slots whose high word is the extreme" rule."""
     from dxa.engine import window_dense
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store()
+    store = new_store(6)
     seen = {"lo": 0, "split": 0}
 
-    def each(b, q, rows):
+    def each(b, q, rows, view, table):
         for r in rows:
             if r["deviceId"] == 100:
                 assert r["sb"] < 0 and r["mxb"] < 0 and r["sw"] < 0 and r["mxw"] < 0 and r["aw"] < 0, r
@@ -480,7 +334,7 @@ def test_carries_and_signs(gpu, monkeypatch):
                 assert mx >> 64 == 5 and (mx & (HI - 1)) < 100 and mn >> 64 == 4 and (mn & (HI - 1)) > HALF, r
                 seen["split"] += 1
 
-    run_stream(carry_stream(14), [Q_CARRY], gpu, store, each)
+    run_stream(carry_stream(14), [Q_CARRY], gpu, store, TYPED, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert seen["lo"] > 14 and seen["split"] > 6, seen
@@ -490,9 +344,9 @@ def test_carries_and_signs(gpu, monkeypatch):
 def test_avg_ties_round_away_from_zero(gpu):
     """Groups of exactly 32 and 64 rows over four panes whose quotient at scale s + 4 is an exact half (or, 64 rows
     and an odd sum, a quarter), positive and negative; a one-row group; a group whose argument is always NULL."""
-    store = new_store()
+    store = new_store(6)
     seen = {"null": 0, "one": 0, "tie": set()}
-    run_stream(ties_stream(14), [Q_TIES], gpu, store, tie_checker(seen))
+    run_stream(ties_stream(14), [Q_TIES], gpu, store, TYPED, tie_checker(seen))
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert seen["tie"] == {3201, 3202, 6401, 6402, 6403, 6404} and seen["null"] > 14 and seen["one"] > 7, seen
@@ -504,19 +358,12 @@ def test_straddles_the_lds_bound(gpu, monkeypatch):
     a second statement whose three groups are all summed in LDS."""
     from dxa.engine import window_dense
     from dxa.ops import native as N
-    import numpy as np
     L = N.lib().dxa_win_m2_lds_groups()
     assert L > 0
     if L + 200 > window_dense.DENSE_GROUPS:
         monkeypatch.setattr(window_dense, "DENSE_GROUPS", 2 * (L + 200))
-    rng = np.random.default_rng(37)
-    stream = []
-    for b in range(9):
-        ids = np.repeat(np.arange(L + 200), 2)
-        rng.shuffle(ids)
-        stream.append(((100 + b) * S, batch(rng, (100 + b) * S, ids), ids))
-    store = new_store()
-    run_stream(stream, [Q_SMALL, Q_MOD], gpu, store)
+    store = new_store(6)
+    run_stream(two_rows_per_id_stream(batch, 9, L + 200), [Q_SMALL, Q_MOD], gpu, store, TYPED)
     states = list(dense_states(store).values())
     assert len(states) == 2 and not any(d.disabled for d in states)
     assert all(len(d.layout["decargs"]) == 4 for d in states)
@@ -528,8 +375,8 @@ def test_rebuild_moves_the_decimal_words(gpu, monkeypatch):
     low-key line with the others, and the 2-pane blocks are combined again afterwards."""
     from dxa.ops.groupby import _MA_LOKEY
     set_caps(monkeypatch, 16, 64, 1 << 16, 1 << 20, block=2)
-    store = new_store()
-    run_stream(churn_stream(40), [Q_SMALL], gpu, store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 40), [Q_SMALL], gpu, store, TYPED)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert d.rebuilds > 0 and d.gcap <= 64 and _MA_LOKEY in d.layout["line_ops"]
@@ -537,29 +384,13 @@ def test_rebuild_moves_the_decimal_words(gpu, monkeypatch):
 
 @pytest.mark.gpu
 def test_partials_at_world_size_one(gpu, monkeypatch):
-    """The N-rank form at world size 1 (the patching of test_window_dense_comoments.py): the ring hands
-    ``merge_partials`` the decimal states of ``distagg._partials``, two-lane ones as [n, 2]."""
-    from dxa import parallel as P
-    from dxa.engine import distagg, window_dense
-    monkeypatch.setattr(P, "active", lambda: True)
-    monkeypatch.setattr(distagg, "exchange_partials", lambda partial, key_names, grouped: (partial, P.HASHED))
-    calls = {"n": 0}
-    real = window_dense.dense_partials
-
-    def counted(*a, **k):
-        got = real(*a, **k)
-        calls["n"] += got is not None
-        return got
-
-    monkeypatch.setattr(window_dense, "dense_partials", counted)
-
-    def prepare(view):
-        view.dist = P.PARTITIONED
-
-    store = new_store()
-    stream = churn_stream(12)
+    """The N-rank form at world size 1 (``as_partitioned_world_of_one``): the ring hands ``merge_partials`` the
+    decimal states of ``distagg._partials``, two-lane ones as [n, 2]."""
+    calls, prepare = as_partitioned_world_of_one(monkeypatch)
+    store = new_store(6)
+    stream = churn_stream(batch, 12)
     q = Q_ALL.replace(", COUNT(DISTINCT kind) AS dk", "")       # (a distinct count has no mergeable partial)
-    run_stream(stream, [q], gpu, store, prepare=prepare)
+    run_stream(stream, [q], gpu, store, TYPED, prepare=prepare)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert calls["n"] >= len(stream) - 4          # (the watermark keeps the first windows empty)
@@ -567,8 +398,8 @@ def test_partials_at_world_size_one(gpu, monkeypatch):
 
 @pytest.mark.gpu
 def test_sum_beyond_28_digits_keeps_the_paned_path(gpu):
-    store = new_store()
-    run_stream(churn_stream(10), [Q_P30], gpu, store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 10), [Q_P30], gpu, store, TYPED)
     d = only_state(store)
     assert d.disabled and d.disabled_reason == "decimal precision"
 
@@ -580,27 +411,15 @@ def test_one_decimal_pass_per_accumulated_pane(gpu, monkeypatch, q, dec):
     ``dxa_win_dec`` once per accumulated pane, right after the multi-aggregate, and nothing more per answer; a layout
     without them never calls it and hands the combine no low-key descriptor."""
     from dxa.engine import window_dense
-    from launch_count import count_launches
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store()
+    store = new_store(6)
     pane = ["dxa_win_insert_fused", "dxa_aggregate_multi", *["dxa_win_dec"] * dec]
     completed_seen = set()
-    for b, (T, tbl, _ids) in enumerate(small_stream(14)):
-        views, _ = store.process(tbl.to(gpu), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        states = list(dense_states(store).values())
-        before = set(states[0].blocks) if states else set()
-        with count_launches() as log:
-            out = run_sql(q, cat, EvalContext(now_us=0, device=gpu))
-        assert_rows(rows_of(out), oracle(q, views["W"]), (b, q))
-        if b < 8:                                   # the watermark and the 6-pane window: full from batch 7 on
-            continue
+    # the watermark and the 6-pane window: full from batch 7 on
+    for b, native, completed in steady_state_launches(gpu, store, small_stream(batch, 14, mid_pane=True), q, TYPED, 8):
         d = only_state(store)
         assert not d.disabled and d.rebuilds == 0
-        completed = len(set(d.blocks) - before)
         completed_seen.add(completed)
-        native = [nm for nm in log if nm.startswith("dxa_")]
         assert native == pane + ["dxa_win_combine_block"] * completed + ["dxa_win_answer"], (b, native)
     assert completed_seen == {0, 1}
     d = only_state(store)

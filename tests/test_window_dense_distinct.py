@@ -2,20 +2,17 @@
 win_pair_mark / win_distinct_fold / win_pair_or): a distinct count is a count of live (group, x) pairs, kept in a
 second persistent dictionary with one presence byte per ring slot.  The oracle is the CPU evaluator over the
 materialised window (no GPU code in it); ``temp`` values are multiples of 0.25, so every row compares exactly."""
-import json
 import struct
-import warnings
 
 import pytest
 import torch
 
 from dxa.engine.column import PrimColumn, Table, strings_from_pylist
 from dxa.engine.expr import EvalContext
-from dxa.engine.query import Catalog, run_sql
-from dxa.engine.serialize import table_to_json_lines
-from dxa.engine.windows import TimeWindowConf, WindowStore
+from tests.window_dense_support import (S, Comparison, aggs_of, answer, batch, churn_stream, dense_states, new_store,
+                                        only_state, oracle, run_stream, set_caps, with_syncs_counted)
 
-S = 1_000_000
+JSON = Comparison("json")
 Q_GRP = ("SELECT deviceId, COUNT(DISTINCT kind) AS dk, COUNT(DISTINCT temp) AS dt, COUNT(*) AS c, MAX(temp) AS mx, "
          "AVG(temp) AS av FROM W GROUP BY deviceId")
 Q_GLOB = "SELECT COUNT(DISTINCT deviceId) AS dd, MAX(ts) AS last FROM W WHERE temp > 8"
@@ -24,102 +21,6 @@ Q_KIND = "SELECT deviceId, COUNT(DISTINCT kind) AS dk, SUM(temp) AS s FROM W GRO
 Q_INT = ("SELECT deviceId, COUNT(*) AS c, SUM(temp) AS s, MIN(temp) AS mn, MAX(temp) AS mx, AVG(temp) AS av "
          "FROM W GROUP BY deviceId")
 ALL = [Q_GRP, Q_GLOB, Q_NONE, Q_KIND]
-STABLE = 200
-
-
-# ---- helpers (copies of tests/test_window_dense_churn.py's) -------------------------------------------------------
-def drifting_ids(rng, b, n):
-    """Batch ``b``'s drifting ids: uniform in [4b, 4b + 12)."""
-    return rng.integers(4 * b, 4 * b + 12, n)
-
-
-def batch(rng, t_us, ids):
-    """tests/test_windows.py::batch with given device ids and exactly summable temperatures."""
-    n = len(ids)
-    ts = torch.tensor([t_us - int(rng.integers(0, S - 1)) for _ in range(n)], dtype=torch.int64)
-    temp = torch.tensor(rng.integers(0, 256, n) * 0.25, dtype=torch.float64)
-    valid = torch.tensor(rng.random(n) > 0.1)
-    kinds = strings_from_pylist([["a", "b", "c"][int(i) % 3] for i in rng.integers(0, 3, n)], "cpu")
-    return Table(["ts", "deviceId", "kind", "temp"],
-                 [PrimColumn("timestamp", ts), PrimColumn("long", torch.tensor(ids, dtype=torch.int64)), kinds,
-                  PrimColumn("double", temp, valid)], n, "cpu")
-
-
-def churn_stream(nb):
-    """200 rows per batch over the drifting ids → [(batch time, CPU table, ids)]."""
-    import numpy as np
-    rng = np.random.default_rng(23)
-    out = []
-    for b in range(nb):
-        ids = drifting_ids(rng, b, 200)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids), ids))
-    return out
-
-
-def stable_stream(nb, drift):
-    """300 rows per batch: 200 over the stable ids and 100 over the drifting ids (or all 300 stable)."""
-    import numpy as np
-    rng = np.random.default_rng(29)
-    out = []
-    for b in range(nb):
-        ids = rng.integers(1000, 1000 + STABLE, 300)
-        if drift:
-            ids[200:] = drifting_ids(rng, b, 100)
-        out.append(((100 + b) * S, batch(rng, (100 + b) * S, ids), ids))
-    return out
-
-
-def _canon(t):
-    out = []
-    for r in (json.loads(x) for x in table_to_json_lines(t)):
-        out.append(tuple(sorted((k, round(v, 6) if isinstance(v, float) else v) for k, v in r.items())))
-    return sorted(out)
-
-
-def oracle(q, view):
-    """The CPU evaluator's rows for statement ``q`` over the materialised window ``view``."""
-    mat = Table(view.names, view.columns, view.length, view._device)
-    cat = Catalog()
-    cat.register("W", mat.to("cpu"))
-    return _canon(run_sql(q, cat, EvalContext(now_us=0)))
-
-
-def new_store(win=6):
-    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
-
-
-def dense_states(store):
-    return store.__dict__.get("_dense", {})
-
-
-def set_caps(monkeypatch, groups, groups_max, pairs, pairs_max, block=None):
-    from dxa.engine import window_dense
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS", groups)
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", groups_max)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS", pairs)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS_MAX", pairs_max)
-    if block is not None:
-        monkeypatch.setattr(window_dense, "BLOCK", block)
-
-
-def run_stream(stream, qs, dev, store, each=None):
-    """Every statement over every batch's window equals the CPU oracle; ``each(b, q, got, rows)`` after each."""
-    for b, (T, tbl, _ids) in enumerate(stream):
-        views, _ = store.process(tbl.to(dev), T, S)
-        for q in qs:
-            cat = Catalog()
-            cat.register("W", views["W"])
-            got = run_sql(q, cat, EvalContext(now_us=0, device=dev))
-            rows = _canon(got)
-            assert rows == oracle(q, views["W"]), (b, q)
-            if each is not None:
-                each(b, q, got, rows)
-
-
-def only_state(store):
-    states = list(dense_states(store).values())
-    assert len(states) == 1
-    return states[0]
 
 
 def pair_sets(stream, col):
@@ -136,46 +37,36 @@ def most_in(sets, k):
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------
-def _aggs(*select_items):
-    from dxa.engine.query import _collect_aggs
-    from dxa.sql.parser import parse_select_item
-    aggs = {}
-    for item in select_items:
-        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
-    assert aggs
-    return aggs
-
-
 def test_requests_accept_count_distinct_only():
     """COUNT(DISTINCT x) is a request of its own beside the five plain aggregates; every other distinct form and
     approx_count_distinct stay ineligible."""
     from dxa.engine.window_dense import Ineligible, _requests
-    reqs = _requests(_aggs("COUNT(DISTINCT kind)", "COUNT(DISTINCT temp)", "COUNT(*)", "COUNT(temp)", "SUM(temp)",
+    reqs = _requests(aggs_of("COUNT(DISTINCT kind)", "COUNT(DISTINCT temp)", "COUNT(*)", "COUNT(temp)", "SUM(temp)",
                            "MIN(temp)", "MAX(temp)", "AVG(temp)", "COUNT(DISTINCT kind) + 1"))
     funcs = [f for _, f, _ in reqs]
     assert funcs.count("dcount") == 2 and set(funcs) == {"dcount", "count_star", "count", "sum", "min", "max", "avg"}
     for bad in ("SUM(DISTINCT temp)", "AVG(DISTINCT temp)", "COUNT(DISTINCT deviceId, kind)",
                 "approx_count_distinct(kind)"):
         with pytest.raises(Ineligible):
-            _requests(_aggs(bad))
+            _requests(aggs_of(bad))
 
 
 def test_cpu_device_takes_the_generic_path():
     """On a CPU device the four statements equal the oracle and no dense state is created."""
-    store = new_store()
-    run_stream(churn_stream(8), ALL, torch.device("cpu"), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 8), ALL, torch.device("cpu"), store, JSON)
     assert not dense_states(store)
-    T, tbl, _ = churn_stream(1)[0]
-    views, _ = new_store().process(tbl, T, S)
-    assert oracle(Q_NONE, views["W"]) == [(("dd", 0),)]
+    T, tbl, _ = churn_stream(batch, 1)[0]
+    views, _ = new_store(6).process(tbl, T, S)
+    assert oracle(Q_NONE, views["W"], JSON.rows) == [(("dd", 0),)]
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("q,npairs", [(Q_GRP, 2), (Q_GLOB, 1), (Q_NONE, 1)])
 def test_stays_dense(gpu, q, npairs):
-    store = new_store()
-    run_stream(churn_stream(12), [q], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 12), [q], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert len(d.pairs) == npairs
@@ -186,12 +77,12 @@ def test_pairs_recycle(gpu, monkeypatch):
     """504 (id, kind) pairs stream through a 256-pair dictionary that may not grow, and 168 ids through a 64-id
     group dictionary: both recycle, and every group rebuild renumbers the pairs' parents."""
     set_caps(monkeypatch, 64, 64, 256, 256)
-    stream = churn_stream(40)
+    stream = churn_stream(batch, 40)
     pairs = pair_sets(stream, "kind")
     assert len(set().union(*pairs)) == 504
     assert most_in(pairs, 14) <= 192
-    store = new_store()
-    run_stream(stream, [Q_KIND], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(stream, [Q_KIND], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert d.pairs[0].rebuilds >= 1 and d.pairs[0].pcap == 256
@@ -202,12 +93,12 @@ def test_pairs_recycle(gpu, monkeypatch):
 def test_pairs_grow(gpu, monkeypatch):
     """The (id, temp) pairs outgrow 64: the temp pair state's capacity doubles; the (id, kind) pairs still fit."""
     set_caps(monkeypatch, 64, 64, 64, 8192)
-    stream = churn_stream(40)
+    stream = churn_stream(batch, 40)
     pairs = pair_sets(stream, "temp")
     assert len(set().union(*pairs)) <= 6795
     assert most_in(pairs, 16) <= 2754
-    store = new_store()
-    run_stream(stream, [Q_GRP], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(stream, [Q_GRP], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     kind, temp = d.pairs
@@ -219,15 +110,15 @@ def test_pairs_grow(gpu, monkeypatch):
 def test_pair_blocks(gpu, monkeypatch):
     """A 12 s window of 2-pane blocks: presence rows are ORed into block slots, and again after every rebuild."""
     set_caps(monkeypatch, 64, 128, 256, 512, block=2)
-    store = new_store(win=12)
+    store = new_store(12)
     seen = {"blocks": 0}
 
-    def each(b, q, got, rows):
+    def each(b, q, rows, view, got):
         for d in dense_states(store).values():     # (no state before the first rows)
             if d.pairs and not d.disabled:
                 seen["blocks"] = max(seen["blocks"], len(d.blocks))
 
-    run_stream(churn_stream(60), [Q_KIND], torch.device("cuda", 0), store, each)
+    run_stream(churn_stream(batch, 60), [Q_KIND], torch.device("cuda", 0), store, JSON, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert seen["blocks"] > 4
@@ -239,8 +130,8 @@ def test_pair_capacity_reached_falls_back_with_a_reason(gpu, monkeypatch):
     """The temp pairs cannot fit 64 and may not grow: every batch still equals the oracle (the generic path), and
     the state says why."""
     set_caps(monkeypatch, 1 << 16, 1 << 20, 64, 64)
-    store = new_store()
-    run_stream(churn_stream(12), [Q_GRP], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 12), [Q_GRP], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert d.disabled and d.disabled_reason == "pair dictionary full"
 
@@ -273,8 +164,8 @@ Q_SPECIAL = "SELECT grp, COUNT(DISTINCT d) AS dd, COUNT(DISTINCT s) AS ds, COUNT
 @pytest.mark.gpu
 def test_special_values(gpu):
     """-0.0 counts with 0.0, every NaN as one, NULLs never; "" and a 48-byte string are values of their own."""
-    store = new_store()
-    run_stream(_special_stream(48), [Q_SPECIAL], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(_special_stream(48), [Q_SPECIAL], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None and len(d.pairs) == 2
 
@@ -282,8 +173,8 @@ def test_special_values(gpu):
 @pytest.mark.gpu
 def test_special_values_too_long(gpu):
     """A 49-byte string does not fit a dictionary slot: the statement leaves the dense path, rows still exact."""
-    store = new_store()
-    run_stream(_special_stream(49), [Q_SPECIAL], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(_special_stream(49), [Q_SPECIAL], torch.device("cuda", 0), store, JSON)
     d = only_state(store)
     assert d.disabled and d.disabled_reason == "key too long"
 
@@ -295,23 +186,21 @@ def test_deferred(gpu, monkeypatch):
     from dxa.engine.column import DeferredTable
     set_caps(monkeypatch, 64, 64, 256, 256)
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     through_deferred = 0
 
     def rebuilds():
         return sum(d.rebuilds + sum(p.rebuilds for p in d.pairs) for d in dense_states(store).values())
 
-    for b, (T, tbl, _ids) in enumerate(churn_stream(40)):
+    for b, (T, tbl, _ids) in enumerate(churn_stream(batch, 40)):
         views, _ = store.process(tbl.to(dev), T, S)
         ctx = EvalContext(now_us=0, device=dev)
         ctx.defer_dense = True
-        cat = Catalog()
-        cat.register("W", views["W"])
-        got = run_sql(Q_KIND, cat, ctx)
+        got = answer(Q_KIND, views["W"], ctx=ctx)
         if b >= 4:
             assert isinstance(got, DeferredTable) and ctx.pending
         before = rebuilds()
-        assert _canon(got) == oracle(Q_KIND, views["W"]), b
+        JSON.check(Q_KIND, views["W"], got, b)
         through_deferred += rebuilds() > before
     d = only_state(store)
     assert not d.disabled and len(d.pairs) == 1
@@ -323,24 +212,15 @@ def test_one_sync_per_batch_and_plain_statements_unchanged(gpu):
     """A steady-state batch of Q_KIND makes one synchronising read (counted as tools/sync_audit.py counts them), and
     a statement without a distinct count on the same store gets a state with no pair states."""
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     counts = []
-    for b, (T, tbl, _ids) in enumerate(churn_stream(12)):
+    for b, (T, tbl, _ids) in enumerate(churn_stream(batch, 12)):
         views, _ = store.process(tbl.to(dev), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
         torch.cuda.synchronize(dev)
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            torch.cuda.set_sync_debug_mode("warn")
-            try:
-                got = run_sql(Q_KIND, cat, EvalContext(now_us=0, device=dev))
-            finally:
-                torch.cuda.set_sync_debug_mode("default")
-        counts.append(sum("prototype feature" not in str(w.message) for w in caught))
-        assert _canon(got) == oracle(Q_KIND, views["W"]), b
-        got = run_sql(Q_INT, cat, EvalContext(now_us=0, device=dev))
-        assert _canon(got) == oracle(Q_INT, views["W"]), b
+        got, syncs = with_syncs_counted(lambda: answer(Q_KIND, views["W"], dev))
+        counts.append(syncs)
+        JSON.check(Q_KIND, views["W"], got, b)
+        JSON.check(Q_INT, views["W"], answer(Q_INT, views["W"], dev), b)
     print("synchronising calls per batch:", counts)
     assert counts[-4:] == [1, 1, 1, 1]
     states = list(dense_states(store).values())

@@ -7,17 +7,17 @@ zero sum may differ in sign from the generic path, which ``==`` does not see), r
 multiples of 0.25 below 2^20, so every f64 sum is exact in any order."""
 import math
 import struct
-import warnings
 
 import pytest
 import torch
 
 from dxa.engine.column import PrimColumn, Table, strings_from_pylist
 from dxa.engine.expr import EvalContext
-from dxa.engine.query import Catalog, run_sql
-from dxa.engine.windows import TimeWindowConf, WindowStore
+from tests.window_dense_support import (S, Comparison, aggs_of, answer, churn_stream, dense_states, materialised,
+                                        new_store, only_state, oracle, rows_of, run_stream, set_caps,
+                                        with_syncs_counted)
 
-S = 1_000_000
+SAME = Comparison("tolerant", types=True)       # no tolerance: a float equals the oracle's under ==, NaN with NaN
 Q_MIX = ("SELECT deviceId, COUNT(*) AS c, AVG(t) AS av, COUNT(DISTINCT k) AS dk, SUM(DISTINCT k) AS sk, "
          "AVG(DISTINCT k) AS ak, SUM(DISTINCT t) AS st, approx_count_distinct(k) AS ap, count(DISTINCT k, t) AS dkt, "
          "SUM(DISTINCT k) + 1 AS sk1 FROM W GROUP BY deviceId")
@@ -37,7 +37,6 @@ Q_SUMS = ("SELECT deviceId, COUNT(*) AS c, COUNT(DISTINCT k) AS dk, SUM(DISTINCT
           "FROM W GROUP BY deviceId")
 
 
-# ---- helpers (the pattern of tests/test_window_dense_distinct.py) ---------------------------------------------------
 def table(T, n, ids, cols, mid_pane=False):
     """One batch: ``ts`` spread over the batch's second, every eighth row at the batch time itself — the one instant
     of the window's oldest pane that is still in range, so that pane is clipped into a scratch slot (``mid_pane``:
@@ -63,88 +62,26 @@ def table(T, n, ids, cols, mid_pane=False):
     return Table(names, out, n, "cpu")
 
 
-def churn_stream(nb, rows=200, few=False, mid_pane=False, seed=23):
-    """``rows`` rows per batch over drifting ids (uniform in [4b, 4b + 12)) → [(batch time, CPU table, ids)].  ``k``
-    long, ``t`` double multiples of 0.25 with |t| < 2^20, both with NULLs, ``kind`` a string.  ``few``: k takes three
-    values and kind follows k, so an id has at most three (id, k) pairs and three (id, k, kind) tuples."""
-    import numpy as np
-    rng = np.random.default_rng(seed)
-    out = []
-    for b in range(nb):
-        T = (100 + b) * S
-        ids = rng.integers(4 * b, 4 * b + 12, rows)
-        if few:
-            k = (rng.integers(0, 3, rows) * 7 - 5).tolist()
-            kind = ["abc"[(v + 5) // 7] for v in k]
-        else:
-            k = rng.integers(-40, 40, rows).tolist()
-            kind = ["abc"[int(v)] for v in rng.integers(0, 3, rows)]
-        t = (rng.integers(-(1 << 22) + 1, 1 << 22, rows) // (1 << 14) * (1 << 14) * 0.25).tolist()    # 512 values
-        cols = [("k", "long", k, (rng.random(rows) > 0.1).tolist()),
-                ("t", "double", t, (rng.random(rows) > 0.1).tolist()), ("kind", "string", kind, None)]
-        out.append((T, table(T, rows, ids, cols, mid_pane), ids))
-    return out
+def batch(rng, T, ids, few=False, mid_pane=False):
+    """A batch with given device ids: ``k`` long, ``t`` double multiples of 0.25 with |t| < 2^20, both with NULLs,
+    ``kind`` a string.  ``few``: k takes three values and kind follows k, so an id has at most three (id, k) pairs and
+    three (id, k, kind) tuples."""
+    rows = len(ids)
+    if few:
+        k = (rng.integers(0, 3, rows) * 7 - 5).tolist()
+        kind = ["abc"[(v + 5) // 7] for v in k]
+    else:
+        k = rng.integers(-40, 40, rows).tolist()
+        kind = ["abc"[int(v)] for v in rng.integers(0, 3, rows)]
+    t = (rng.integers(-(1 << 22) + 1, 1 << 22, rows) // (1 << 14) * (1 << 14) * 0.25).tolist()    # 512 values
+    cols = [("k", "long", k, (rng.random(rows) > 0.1).tolist()),
+            ("t", "double", t, (rng.random(rows) > 0.1).tolist()), ("kind", "string", kind, None)]
+    return table(T, rows, ids, cols, mid_pane)
 
 
-def _cell(v):
-    return "NaN" if isinstance(v, float) and v != v else v
-
-
-def rows_of(t):
-    """(column names, column types, rows sorted by their first column) — NaN as a token, so rows compare with ==."""
-    t = t.to("cpu") if str(t.device) != "cpu" else t
-    cols = [c.to_pylist() for c in t.columns]
-    rows = sorted((tuple(_cell(v) for v in r) for r in zip(*cols)), key=lambda r: repr(r[0]))
-    return list(t.names), [str(c.dtype) for c in t.columns], rows
-
-
-def window_table(view):
-    return Table(view.names, view.columns, view.length, view._device).to("cpu")
-
-
-def oracle(q, view):
-    """The CPU evaluator's result for statement ``q`` over the materialised window ``view``."""
-    cat = Catalog()
-    cat.register("W", window_table(view))
-    return rows_of(run_sql(q, cat, EvalContext(now_us=0)))
-
-
-def new_store(win=6):
-    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
-
-
-def dense_states(store):
-    return store.__dict__.get("_dense", {})
-
-
-def set_caps(monkeypatch, groups, groups_max, pairs, pairs_max, block=None):
-    from dxa.engine import window_dense
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS", groups)
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", groups_max)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS", pairs)
-    monkeypatch.setattr(window_dense, "DENSE_PAIRS_MAX", pairs_max)
-    if block is not None:
-        monkeypatch.setattr(window_dense, "BLOCK", block)
-
-
-def run_stream(stream, qs, dev, store, each=None):
-    """Every statement over every batch's window equals the CPU oracle, names, types and values;
-    ``each(b, q, views["W"], rows)`` after each."""
-    for b, (T, tbl, _ids) in enumerate(stream):
-        views, _ = store.process(tbl.to(dev), T, S)
-        for q in qs:
-            cat = Catalog()
-            cat.register("W", views["W"])
-            got = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
-            assert got == oracle(q, views["W"]), (b, q)
-            if each is not None:
-                each(b, q, views["W"], got[2])
-
-
-def only_state(store):
-    states = list(dense_states(store).values())
-    assert len(states) == 1
-    return states[0]
+def as_tuples(rows):
+    """``rows_of``'s rows as tuples in column order, NaN as a token, so rows compare with ==."""
+    return [tuple("NaN" if isinstance(v, float) and v != v else v for v in r.values()) for r in rows]
 
 
 def tuple_sets(stream, *cols):
@@ -160,16 +97,6 @@ def most_in(sets, k):
     return max(len(set().union(*sets[b:b + k])) for b in range(len(sets)))
 
 
-def _aggs(*select_items):
-    from dxa.engine.query import _collect_aggs
-    from dxa.sql.parser import parse_select_item
-    aggs = {}
-    for item in select_items:
-        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
-    assert aggs
-    return aggs
-
-
 # ---- CPU ------------------------------------------------------------------------------------------------------------
 NEW_FORMS = ("SUM(DISTINCT t)", "AVG(DISTINCT t)", "COUNT(DISTINCT k, t)", "count(DISTINCT k, t, kind, deviceId)",
              "approx_count_distinct(k)", "approx_count_distinct(k, 0.05)")
@@ -179,10 +106,10 @@ def test_requests_accept_the_new_forms_under_their_keyword_only():
     from dxa.engine.window_dense import Ineligible, _requests
     for form in NEW_FORMS:
         with pytest.raises(Ineligible):
-            _requests(_aggs(form))
+            _requests(aggs_of(form))
         with pytest.raises(Ineligible):
-            _requests(_aggs(form), picks=True)
-    reqs = _requests(_aggs(*NEW_FORMS, "COUNT(DISTINCT t)", "SUM(DISTINCT t) + 1", "COUNT(*)"), distinct_sums=True)
+            _requests(aggs_of(form), picks=True)
+    reqs = _requests(aggs_of(*NEW_FORMS, "COUNT(DISTINCT t)", "SUM(DISTINCT t) + 1", "COUNT(*)"), distinct_sums=True)
     assert [f for _, f, _ in reqs] == ["dsum", "davg", "dcount", "dcount", "dcount", "dcount", "dcount", "count_star"]
     assert [len(a) for _, f, a in reqs if isinstance(a, tuple)] == [2, 4]
     # the one-argument forms of k share a key, rsd or not; a tuple is a key of its own
@@ -194,9 +121,9 @@ def test_requests_accept_the_new_forms_under_their_keyword_only():
                      ("MIN(DISTINCT t)", "min distinct"), ("stddev(DISTINCT t)", "stddev distinct"),
                      ("SUM(DISTINCT k, t)", "sum distinct")):
         with pytest.raises(Ineligible, match=why):
-            _requests(_aggs(bad), distinct_sums=True)
+            _requests(aggs_of(bad), distinct_sums=True)
     with pytest.raises(Ineligible, match="too many distinct arguments"):
-        _requests(_aggs("SUM(DISTINCT k)", "AVG(DISTINCT t)", "COUNT(DISTINCT kind)", "approx_count_distinct(ts)",
+        _requests(aggs_of("SUM(DISTINCT k)", "AVG(DISTINCT t)", "COUNT(DISTINCT kind)", "approx_count_distinct(ts)",
                         "COUNT(DISTINCT k, t)"), distinct_sums=True)
 
 
@@ -206,7 +133,7 @@ def test_layout_shares_the_dcount_slot():
     double sum and every average, an MA_ADD_U64 word for the integral sum."""
     from dxa.engine.window_dense import _requests, plan_layout
     from dxa.ops.groupby import _F_AVG, _F_COUNT, _F_F64, _F_I64, _MA_ADD_F64, _MA_ADD_U64, _MV_COUNT
-    reqs = _requests(_aggs("COUNT(DISTINCT t)", "SUM(DISTINCT t)", "AVG(DISTINCT t)", "approx_count_distinct(t)",
+    reqs = _requests(aggs_of("COUNT(DISTINCT t)", "SUM(DISTINCT t)", "AVG(DISTINCT t)", "approx_count_distinct(t)",
                            "SUM(DISTINCT k)", "AVG(DISTINCT k)", "count(DISTINCT k, t)", "COUNT(*)"),
                      distinct_sums=True)
     kt, kk = ("id", "t"), ("id", "k")
@@ -225,7 +152,7 @@ def test_layout_shares_the_dcount_slot():
     assert L["as_f64"] == [False, True, True, False, False, True, False, False]
     assert L["pfin"] == {("call", "count", False, True): {"cnt": (_F_COUNT, 8, -1)}}     # no mergeable partial
     # a float argument sums as a double; an int argument as a long
-    L = plan_layout(_requests(_aggs("SUM(DISTINCT t)", "SUM(DISTINCT k)"), distinct_sums=True),
+    L = plan_layout(_requests(aggs_of("SUM(DISTINCT t)", "SUM(DISTINCT k)"), distinct_sums=True),
                     {kt: ("float", True), kk: ("int", False)})
     assert L["dsum_words"] == {kt: (-1, 10), kk: (0, -1)} and [p[4] for p in L["plan"]] == ["double", "long"]
 
@@ -237,7 +164,7 @@ def test_layout_refuses_other_argument_types():
                              ("SUM(DISTINCT ts)", "timestamp", "sum type"), ("AVG(DISTINCT b)", "boolean", "avg type"),
                              ("SUM(DISTINCT d)", parse_decimal_type("decimal(10,2)"), "argument type"),
                              ("AVG(DISTINCT d)", parse_decimal_type("decimal(10,2)"), "argument type")):
-        reqs = _requests(_aggs(item), distinct_sums=True)
+        reqs = _requests(aggs_of(item), distinct_sums=True)
         with pytest.raises(Ineligible, match=why):
             plan_layout(reqs, {reqs[0][2].key(): (dtype, False)})
 
@@ -246,7 +173,7 @@ def test_count_distinct_layout_is_the_one_it_was():
     """A layout with only COUNT(DISTINCT …) beside plain aggregates: the literal values the layout had before the
     distinct sums existed (no ``dsum_words`` key, the same slots, words and recipes)."""
     from dxa.engine.window_dense import _requests, plan_layout
-    reqs = _requests(_aggs("COUNT(DISTINCT kind)", "COUNT(DISTINCT temp)", "COUNT(*)", "SUM(temp)", "AVG(temp)",
+    reqs = _requests(aggs_of("COUNT(DISTINCT kind)", "COUNT(DISTINCT temp)", "COUNT(*)", "SUM(temp)", "AVG(temp)",
                            "MAX(temp)"), distinct_sums=True)
     L = plan_layout(reqs, {("id", "temp"): ("double", True)})
     L.pop("pfin")
@@ -275,12 +202,12 @@ def test_count_distinct_layout_is_the_one_it_was():
 
 def test_cpu_device_takes_the_generic_path():
     """On a CPU device the statements equal the oracle and no dense state is created."""
-    store = new_store()
-    run_stream(churn_stream(8), [Q_MIX, Q_GLOB, Q_NONE], torch.device("cpu"), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 8), [Q_MIX, Q_GLOB, Q_NONE], torch.device("cpu"), store, SAME)
     assert not dense_states(store)
-    T, tbl, _ = churn_stream(1)[0]
-    views, _ = new_store().process(tbl, T, S)
-    assert oracle(Q_NONE, views["W"])[2] == [(0, None, None, 0, 0)]
+    T, tbl, _ = churn_stream(batch, 1)[0]
+    views, _ = new_store(6).process(tbl, T, S)
+    assert as_tuples(oracle(Q_NONE, views["W"])[0]) == [(0, None, None, 0, 0)]
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
@@ -289,13 +216,13 @@ def test_mixed_statement_stays_dense(gpu):
     """Plain aggregates, the three aggregates of one distinct argument, a double distinct sum, approx_count_distinct,
     a two-column distinct count and a distinct sum inside an expression: one state, three pair states (k, t and
     (k, t)), one fold each; some pane is clipped on the way."""
-    store = new_store()
+    store = new_store(6)
     seen = {"clipped": 0}
 
-    def each(b, q, view, rows):
+    def each(b, q, rows, view, table):
         seen["clipped"] += any(not full for _pane, full in view.pieces())
 
-    run_stream(churn_stream(12), [Q_MIX], torch.device("cuda", 0), store, each)
+    run_stream(churn_stream(batch, 12), [Q_MIX], torch.device("cuda", 0), store, SAME, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert len(d.pairs) == 3 and [len(ps.keys) for ps in d.pairs] == [2, 2, 3]
@@ -305,8 +232,8 @@ def test_mixed_statement_stays_dense(gpu):
 
 @pytest.mark.gpu
 def test_one_pair_state_for_the_three_aggregates_of_one_argument(gpu):
-    store = new_store()
-    run_stream(churn_stream(8), [Q_SUMS], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 8), [Q_SUMS], torch.device("cuda", 0), store, SAME)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None and len(d.pairs) == 1
 
@@ -331,14 +258,14 @@ def test_wave_reduction_at_chunk_and_wave_boundaries(gpu, npairs):
     """15 / 16 / 17 live pairs straddle a lane's 16-pair chunk, 1025 a whole wave's 64 × 16: in the global form whole
     waves share the one parent, in the grouped form a ballot has three leaders."""
     assert npairs in (15, 16, 17) or npairs > 64 * 16
-    store = new_store()
+    store = new_store(6)
     stream = _exact_stream(8, npairs)
 
-    def each(b, q, view, rows):
+    def each(b, q, rows, view, table):
         if q == Q_GLOB and b == len(stream) - 1:
-            assert rows[0][0] == npairs and rows[0][5] == npairs
+            assert rows[0]["dt"] == npairs and rows[0]["dkt"] == npairs
 
-    run_stream(stream, [Q_GLOB, Q_GRP], torch.device("cuda", 0), store, each)
+    run_stream(stream, [Q_GLOB, Q_GRP], torch.device("cuda", 0), store, SAME, each)
     states = list(dense_states(store).values())
     assert len(states) == 2
     for d in states:
@@ -369,13 +296,13 @@ def test_nulls(gpu):
     not counted."""
     q = ("SELECT deviceId, SUM(DISTINCT k) AS sk, AVG(DISTINCT k) AS ak, COUNT(DISTINCT k) AS dk, "
          "approx_count_distinct(k) AS ap, count(DISTINCT k, t) AS dkt, count(DISTINCT t) AS dt FROM W GROUP BY deviceId")
-    store = new_store()
+    store = new_store(6)
     seen = []
 
-    def each(b, _q, view, rows):
-        seen.extend(r for r in rows if r[0] == 0)
+    def each(b, _q, rows, view, table):
+        seen.extend(r for r in as_tuples(rows) if r[0] == 0)
 
-    run_stream(_null_stream(8), [q], torch.device("cuda", 0), store, each)
+    run_stream(_null_stream(8), [q], torch.device("cuda", 0), store, SAME, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert seen and all(r[1:6] == (None, None, 0, 0, 0) and r[6] > 0 for r in seen)
@@ -407,13 +334,13 @@ def test_special_doubles_and_wrapping_longs(gpu):
     under ==, NaN with NaN; the long sum wraps as the oracle's does."""
     q = ("SELECT grp, SUM(DISTINCT d) AS sd, AVG(DISTINCT d) AS ad, COUNT(DISTINCT d) AS dd, SUM(DISTINCT k) AS sk, "
          "COUNT(DISTINCT k) AS dk, count(DISTINCT d, k) AS ddk FROM W GROUP BY grp")
-    store = new_store()
+    store = new_store(6)
     last = {}
 
-    def each(b, _q, view, rows):
-        last["rows"] = rows
+    def each(b, _q, rows, view, table):
+        last["rows"] = as_tuples(rows)
 
-    run_stream(_special_stream(8), [q], torch.device("cuda", 0), store, each)
+    run_stream(_special_stream(8), [q], torch.device("cuda", 0), store, SAME, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     by = {r[0]: r for r in last["rows"]}
@@ -433,7 +360,7 @@ def test_float_and_int_arguments(gpu):
     q = "SELECT deviceId, SUM(DISTINCT f) AS sf, AVG(DISTINCT f) AS af, SUM(DISTINCT i) AS si, AVG(DISTINCT i) AS ai " \
         "FROM W GROUP BY deviceId"
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     for b in range(8):
         T = (100 + b) * S
         n = 64
@@ -441,12 +368,10 @@ def test_float_and_int_arguments(gpu):
         cols = [("f", "float", (rng.integers(-64, 64, n) * 0.25).tolist(), (rng.random(n) > 0.1).tolist()),
                 ("i", "int", rng.integers(-30, 30, n).tolist(), (rng.random(n) > 0.1).tolist())]
         views, _ = store.process(table(T, n, ids, cols).to(dev), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        names, types, rows = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
+        rows, types = rows_of(answer(q, views["W"], dev))
         if rows:
-            assert types == ["long", "double", "double", "long", "double"]
-        assert rows == oracle(q, views["W"])[2], b
+            assert list(types.values()) == ["long", "double", "double", "long", "double"]
+        assert as_tuples(rows) == as_tuples(oracle(q, views["W"])[0]), b
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None and len(d.pairs) == 2
 
@@ -457,12 +382,12 @@ def test_pairs_recycle_with_sums_and_two_columns(gpu, monkeypatch):
     dictionary and 256-pair dictionaries that may not grow: both pair states recycle, and every group rebuild
     renumbers their parents."""
     set_caps(monkeypatch, 64, 64, 256, 256)
-    stream = churn_stream(40, few=True)
+    stream = churn_stream(batch, 40, few=True)
     for cols in (("k",), ("k", "kind")):
         sets = tuple_sets(stream, *cols)
         assert len(set().union(*sets)) > 256 and most_in(sets, 14) <= 192
-    store = new_store()
-    run_stream(stream, [Q_LIFE], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(stream, [Q_LIFE], torch.device("cuda", 0), store, SAME)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert len(d.pairs) == 2 and len(d.pairs[1].keys) == 3
@@ -475,10 +400,10 @@ def test_pairs_grow_with_sums_and_two_columns(gpu, monkeypatch):
     """The (id, t) pairs and the (id, t, k) tuples outgrow 64: both dictionaries double (their value columns move)
     while the 64-id group dictionary recycles under them."""
     set_caps(monkeypatch, 64, 64, 64, 8192)
-    stream = churn_stream(30)
+    stream = churn_stream(batch, 30)
     assert most_in(tuple_sets(stream, "t", "k"), 16) <= 4096
-    store = new_store()
-    run_stream(stream, [Q_WIDE], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(stream, [Q_WIDE], torch.device("cuda", 0), store, SAME)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert len(d.pairs) == 2 and d.rebuilds >= 1
@@ -489,15 +414,15 @@ def test_pairs_grow_with_sums_and_two_columns(gpu, monkeypatch):
 def test_pair_blocks(gpu, monkeypatch):
     """A 12 s window of 2-pane blocks: the sums are folded from block slots' presence rows, and again after rebuilds."""
     set_caps(monkeypatch, 64, 128, 256, 512, block=2)
-    store = new_store(win=12)
+    store = new_store(12)
     seen = {"blocks": 0}
 
-    def each(b, q, view, rows):
+    def each(b, q, rows, view, table):
         for d in dense_states(store).values():
             if d.pairs and not d.disabled:
                 seen["blocks"] = max(seen["blocks"], len(d.blocks))
 
-    run_stream(churn_stream(36, few=True), [Q_LIFE], torch.device("cuda", 0), store, each)
+    run_stream(churn_stream(batch, 36, few=True), [Q_LIFE], torch.device("cuda", 0), store, SAME, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None
     assert seen["blocks"] > 4
@@ -507,13 +432,13 @@ def test_pair_blocks(gpu, monkeypatch):
 @pytest.mark.gpu
 def test_empty_window_of_the_global_form(gpu):
     """Nothing passes the WHERE: Spark's one row — the counts 0, the sum and the average NULL."""
-    store = new_store()
+    store = new_store(6)
     seen = []
 
-    def each(b, q, view, rows):
-        seen.append(rows)
+    def each(b, q, rows, view, table):
+        seen.append(as_tuples(rows))
 
-    run_stream(churn_stream(6), [Q_NONE], torch.device("cuda", 0), store, each)
+    run_stream(churn_stream(batch, 6), [Q_NONE], torch.device("cuda", 0), store, SAME, each)
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None and d.global_form
     assert seen[-1] == [(0, None, None, 0, 0)]
@@ -526,23 +451,21 @@ def test_deferred(gpu, monkeypatch):
     from dxa.engine.column import DeferredTable
     set_caps(monkeypatch, 64, 64, 256, 256)
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     through_deferred = 0
 
     def rebuilds():
         return sum(d.rebuilds + sum(p.rebuilds for p in d.pairs) for d in dense_states(store).values())
 
-    for b, (T, tbl, _ids) in enumerate(churn_stream(40, few=True)):
+    for b, (T, tbl, _ids) in enumerate(churn_stream(batch, 40, few=True)):
         views, _ = store.process(tbl.to(dev), T, S)
         ctx = EvalContext(now_us=0, device=dev)
         ctx.defer_dense = True
-        cat = Catalog()
-        cat.register("W", views["W"])
-        got = run_sql(Q_LIFE, cat, ctx)
+        got = answer(Q_LIFE, views["W"], ctx=ctx)
         if b >= 4:
             assert isinstance(got, DeferredTable) and ctx.pending
         before = rebuilds()
-        assert rows_of(got) == oracle(Q_LIFE, views["W"]), b
+        SAME.check(Q_LIFE, views["W"], got, b)
         through_deferred += rebuilds() > before
     d = only_state(store)
     assert not d.disabled and d.disabled_reason is None and len(d.pairs) == 2
@@ -554,8 +477,8 @@ def test_pair_capacity_reached_falls_back_with_a_reason(gpu, monkeypatch):
     """The (id, t) pairs cannot fit 64 and may not grow: every batch still equals the oracle (the generic path), and
     the state says why."""
     set_caps(monkeypatch, 1 << 16, 1 << 20, 64, 64)
-    store = new_store()
-    run_stream(churn_stream(10), [Q_WIDE], torch.device("cuda", 0), store)
+    store = new_store(6)
+    run_stream(churn_stream(batch, 10), [Q_WIDE], torch.device("cuda", 0), store, SAME)
     d = only_state(store)
     assert d.disabled and d.disabled_reason == "pair dictionary full"
 
@@ -571,7 +494,7 @@ def test_arbitrary_doubles_within_the_reordering_bound(gpu):
     pool = rng.standard_normal(400) * 1e6
     q = "SELECT deviceId, SUM(DISTINCT x) AS sx, COUNT(DISTINCT x) AS dx FROM W GROUP BY deviceId"
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     worst = 0.0
     for b in range(8):
         T = (100 + b) * S
@@ -579,16 +502,16 @@ def test_arbitrary_doubles_within_the_reordering_bound(gpu):
         ids = rng.integers(0, 3, n)
         x = pool[rng.integers(0, len(pool), n)].tolist()
         views, _ = store.process(table(T, n, ids, [("x", "double", x, None)]).to(dev), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        names, types, got = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
-        want = oracle(q, views["W"])
-        assert (names, types) == want[:2] and [r[0] for r in got] == [r[0] for r in want[2]]
-        w = window_table(views["W"])
+        got, types = rows_of(answer(q, views["W"], dev))
+        want, wtypes = oracle(q, views["W"])
+        assert list(types.items()) == list(wtypes.items())
+        got, want = as_tuples(got), as_tuples(want)
+        assert [r[0] for r in got] == [r[0] for r in want]
+        w = materialised(views["W"])
         values = {}
         for g, v in zip(w.column("deviceId").to_pylist(), w.column("x").to_pylist()):
             values.setdefault(g, set()).add(v)
-        for (g, sx, dx), (_g, wsx, wdx) in zip(got, want[2]):
+        for (g, sx, dx), (_g, wsx, wdx) in zip(got, want):
             vals = values[g]
             bound = (len(vals) - 1) * 2.0 ** -52 * sum(abs(v) for v in vals)
             print(f"batch {b} group {g}: n {len(vals)} |got - want| {abs(sx - wsx):.3e} bound {bound:.3e}")
@@ -612,33 +535,25 @@ def test_entry_points_and_one_sync_per_steady_state_batch(gpu, monkeypatch, q):
     from launch_count import count_launches
     monkeypatch.setattr(window_dense, "BLOCK", 2)
     dev = torch.device("cuda", 0)
-    store = new_store()
+    store = new_store(6)
     pane = ["dxa_win_insert_fused", "dxa_aggregate_multi", "dxa_win_pair_prep", "dxa_win_insert_fused",
             "dxa_win_pair_mark"]
     block = ["dxa_win_combine_block", "dxa_win_pair_or_block"]
     completed_seen = set()
     syncs = []
-    for b, (T, tbl, _ids) in enumerate(churn_stream(16, rows=64, few=True, mid_pane=True)):
+    for b, (T, tbl, _ids) in enumerate(churn_stream(batch, 16, rows=64, few=True, mid_pane=True)):
         views, _ = store.process(tbl.to(dev), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
         states = list(dense_states(store).values())
         before = set(states[0].blocks) if states else set()
         torch.cuda.synchronize(dev)
         if b % 3:
             with count_launches() as log:
-                out = run_sql(q, cat, EvalContext(now_us=0, device=dev))
+                out = answer(q, views["W"], dev)
         else:
             log = None
-            with warnings.catch_warnings(record=True) as caught:
-                warnings.simplefilter("always")
-                torch.cuda.set_sync_debug_mode("warn")
-                try:
-                    out = run_sql(q, cat, EvalContext(now_us=0, device=dev))
-                finally:
-                    torch.cuda.set_sync_debug_mode("default")
-            syncs.append(sum("prototype feature" not in str(w.message) for w in caught))
-        assert rows_of(out) == oracle(q, views["W"]), b
+            out, n = with_syncs_counted(lambda: answer(q, views["W"], dev))
+            syncs.append(n)
+        SAME.check(q, views["W"], out, b)
         if b < 8 or log is None:                    # the watermark and the 6-pane window: full from batch 7 on
             continue
         d = only_state(store)

@@ -14,11 +14,11 @@ import pytest
 import torch
 
 from dxa.engine.column import PrimColumn, Table, strings_from_pylist
-from dxa.engine.expr import EvalContext
-from dxa.engine.query import Catalog, run_sql
-from dxa.engine.windows import TimeWindowConf, WindowStore
+from tests.window_dense_support import (S, Comparison, aggs_of, as_partitioned_world_of_one, churn_stream,
+                                        dense_states, layout_of, materialised, new_store, on_the_ring, only_state,
+                                        run_stream, set_caps, steady_state_launches, two_rows_per_id_stream)
 
-S = 1_000_000
+BITS = Comparison("bits", order_by="deviceId")
 D18 = "CAST(serial AS DECIMAL(18,2))"
 YDEC = "CAST(y3 AS DECIMAL(10,1))"
 Q_MIXED = ("SELECT deviceId, COUNT(*) AS c, first(serial) AS f, last(serial) AS l, max_by(serial, y3) AS mx, "
@@ -40,7 +40,6 @@ Q_PLAIN = ("SELECT deviceId, COUNT(*) AS c, SUM(y3) AS s, MIN(y3) AS mn, MAX(y3)
 NAN = float("nan")
 
 
-# ---- helpers (the ``oracle`` / ``rows_of`` pattern of tests/test_window_dense_decimal.py) ---------------------------
 def batch(rng, b, T, ids, spread, bait=False):
     """Batch ``b`` with the given device ids, event times within ``spread`` before ``T``.  ``serial`` is unique over the
     stream (so a wrong pick shows); ``y3`` is drawn from three values with NULLs (every group ties inside a pane and
@@ -100,58 +99,13 @@ def small_stream(nb, groups=4, rows=40, whole=True, bait=False, seed=43):
         rng.shuffle(ids)
         T = (100 + b) * S
         out.append((T, batch(rng, b, T - S // 4, ids, S // 2, bait) if whole else
-                    batch(rng, b, T - S // 2, ids, S - 1, bait)))
+                    batch(rng, b, T - S // 2, ids, S - 1, bait), ids))
     return out
 
 
-def rows_of(t):
-    """The table's rows as dicts of Python values (NULL as None), ordered by device id, and its column dtypes."""
-    t = t.to("cpu")
-    cols = {nm: t.column(nm).to_pylist() for nm in t.names}
-    rows = [{nm: cols[nm][i] for nm in t.names} for i in range(t.length)]
-    return sorted(rows, key=lambda r: r["deviceId"]), {nm: str(t.column(nm).dtype) for nm in t.names}
-
-
-def oracle(q, view):
-    """The CPU evaluator's rows and dtypes for statement ``q`` over the materialised window ``view``."""
-    mat = Table(view.names, view.columns, view.length, view._device)
-    cat = Catalog()
-    cat.register("W", mat.to("cpu"))
-    return rows_of(run_sql(q, cat, EvalContext(now_us=0)))
-
-
-def same(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    if isinstance(a, float) and isinstance(b, float):
-        if math.isnan(a) or math.isnan(b):
-            return math.isnan(a) and math.isnan(b)
-        return a == b and math.copysign(1.0, a) == math.copysign(1.0, b)
-    return type(a) is type(b) and a == b and str(a) == str(b)
-
-
-def assert_rows(got, want, what):
-    (got, gtypes), (want, wtypes) = got, want
-    assert gtypes == wtypes, (what, gtypes, wtypes)
-    assert len(got) == len(want), (what, len(got), len(want))
-    for g, w in zip(got, want):
-        assert g.keys() == w.keys(), what
-        for nm in w:
-            assert same(g[nm], w[nm]), (what, nm, g, w)
-
-
-def new_store(win=5):
-    return WindowStore(TimeWindowConf({"W": win * S}, True, "ts", 2 * S, win * S, False))
-
-
-def dense_states(store):
-    return store.__dict__.get("_dense", {})
-
-
-def only_state(store):
-    states = list(dense_states(store).values())
-    assert len(states) == 1
-    return states[0]
+def numbered(rng, T, ids):
+    """``batch`` for the shared stream builders: batch ``T // S - 100``, event times over the whole second."""
+    return batch(rng, T // S - 100, T, ids, S - 1)
 
 
 def newest_first(view):
@@ -167,57 +121,10 @@ def newest_first(view):
     return PanedTable(view.store, panes, view.lo, view.hi, view.names, view._device)
 
 
-def run_stream(stream, qs, dev, store, each=None, prepare=None, reorder=None):
-    """Every statement over every batch's window equals the CPU oracle; ``each(b, q, rows, view)`` after each."""
-    for b, (T, tbl) in enumerate(stream):
-        views, _ = store.process(tbl.to(dev), T, S)
-        view = views["W"] if reorder is None else reorder(views["W"])
-        if prepare is not None:
-            prepare(view)
-        for q in qs:
-            cat = Catalog()
-            cat.register("W", view)
-            got = rows_of(run_sql(q, cat, EvalContext(now_us=0, device=dev)))
-            want = oracle(q, view)
-            assert_rows(got, want, (b, q))
-            if each is not None:
-                each(b, q, got[0], view)
-
-
-def on_the_ring(store, n=1):
-    states = list(dense_states(store).values())
-    assert len(states) == n, len(states)
-    for d in states:
-        assert d.disabled_reason is None and not d.disabled, d.disabled_reason
-    return states
-
-
-def _aggs(*select_items):
-    from dxa.engine.query import _collect_aggs
-    from dxa.sql.parser import parse_select_item
-    aggs = {}
-    for item in select_items:
-        _collect_aggs(parse_select_item(item).expr, EvalContext(now_us=0), aggs)
-    assert aggs
-    return aggs
-
-
 def _layout(aggs):
     import numpy as np
-    from dxa.engine.column import ConstColumn
-    from dxa.engine.expr import Scope, evaluate
-    from dxa.engine.window_dense import _requests, plan_layout
-    empty = batch(np.random.default_rng(0), 0, 100 * S, np.arange(4), S).take(torch.empty(0, dtype=torch.int64))
-    ctx = EvalContext(now_us=0)
-    scope = Scope.of_table(empty, "W")
-    reqs = _requests(aggs, picks=True)
-    types = {}
-    for _, f, arg in reqs:
-        for a in arg if isinstance(arg, tuple) else () if arg is None or f == "dcount" else (arg,):
-            c = evaluate(a, scope, ctx)
-            c = c.materialize() if isinstance(c, ConstColumn) else c
-            types[a.key()] = (c.dtype, getattr(c, "data", torch.empty(0)).dtype == torch.float64)
-    return reqs, plan_layout(reqs, types)
+    reqs, _types, L = layout_of(aggs, batch(np.random.default_rng(0), 0, 100 * S, np.arange(4), S), picks=True)
+    return reqs, L
 
 
 def _words(L):
@@ -234,7 +141,7 @@ def test_layout_of_single_picks():
     from dxa.ops.groupby import (_F_I64, _MA_ADD_F64, _MA_MAX, _MA_PICK_RANK, _MA_PICK_VAL, _MV_I64, _MV_NOT,
                                  _PICK_LAST, _PICK_USED)
     for func, last in (("first", 0), ("last", _PICK_LAST), ("first_value", 0), ("last_value", _PICK_LAST)):
-        aggs = _aggs(f"{func}(temp)")
+        aggs = aggs_of(f"{func}(temp)")
         reqs, L = _layout(aggs)
         assert reqs[0][1] == ("last" if last else "first")
         xk = reqs[0][2].key()
@@ -251,7 +158,7 @@ def test_layout_of_single_picks():
         assert L["fin"] == [(_F_I64, 16, 17)] and L["plan"][0][1:] == ("pick", 2, 3, "double") and L["as_f64"] == [True]
         assert L["pfin"] == {list(aggs)[0]: {"v": (_F_I64, 16, 17)}}
     for func, inv in (("max_by", 0), ("min_by", _MV_NOT)):
-        aggs = _aggs(f"{func}(serial, ts)")
+        aggs = aggs_of(f"{func}(serial, ts)")
         reqs, L = _layout(aggs)
         x, y = reqs[0][2]
         assert L["line_ops"] == [_MA_ADD_F64, _MA_MAX, _MA_PICK_RANK, _MA_PICK_VAL]
@@ -270,7 +177,7 @@ def test_picks_share_rank_and_key_words():
     copy, which MAX(y) does not read."""
     from dxa.engine.window_dense import pick_y_key
     from dxa.ops.groupby import _MA_MAX, _MA_PICK_RANK, _MA_PICK_VAL, _MV_F64_ORD
-    reqs, L = _layout(_aggs("max_by(serial, ts)", "max_by(temp, ts)", "MAX(ts)", "first(serial)", "first(temp)",
+    reqs, L = _layout(aggs_of("max_by(serial, ts)", "max_by(temp, ts)", "MAX(ts)", "first(serial)", "first(temp)",
                             "min_by(serial, ts)", "COUNT(*)"))
     ops = [s[2] for s in L["slots"]]
     assert ops.count(_MA_MAX) == 2 and ops.count(_MA_PICK_RANK) == 3 and ops.count(_MA_PICK_VAL) == 10
@@ -287,7 +194,7 @@ def test_picks_share_rank_and_key_words():
     used = [d for d in L["pickdesc"] if d]
     assert len(used) == 13 and sum(1 for d in used if (d >> 8) & 0xff == kmax + 1) == 5
     # a double y: the pick's key slot reads the copy with -0.0 → 0.0, MAX(yd) keeps its own slot
-    reqs, L = _layout(_aggs("max_by(serial, yd)", "MAX(yd)"))
+    reqs, L = _layout(aggs_of("max_by(serial, yd)", "MAX(yd)"))
     y = reqs[0][2][1]
     keys = [s[0] for s in L["slots"] if s[2] == _MA_MAX]
     assert keys == [("max", pick_y_key(y)), ("max", y.key())]
@@ -299,26 +206,26 @@ def test_refusals_and_layouts_without_picks():
     assert MAX_PICK == 8
     # nine different order keys: nine rank jobs
     with pytest.raises(Ineligible, match="too many pick arguments"):
-        _requests(_aggs(*[f"max_by(serial, y3 + {k})" for k in range(9)]), picks=True)
+        _requests(aggs_of(*[f"max_by(serial, y3 + {k})" for k in range(9)]), picks=True)
     # one rank job, nine payload jobs
     with pytest.raises(Ineligible, match="too many pick arguments"):
-        _requests(_aggs(*[f"first(serial + {k})" for k in range(9)]), picks=True)
-    _requests(_aggs(*[f"first(serial + {k})" for k in range(8)]), picks=True)
-    _requests(_aggs("last(serial)", *[f"max_by(serial, y3 + {k})" for k in range(7)]), picks=True)
+        _requests(aggs_of(*[f"first(serial + {k})" for k in range(9)]), picks=True)
+    _requests(aggs_of(*[f"first(serial + {k})" for k in range(8)]), picks=True)
+    _requests(aggs_of("last(serial)", *[f"max_by(serial, y3 + {k})" for k in range(7)]), picks=True)
     # the two-argument form keeps the reason it had
     with pytest.raises(Ineligible, match="^first$"):
-        _requests(_aggs("first(temp, true)"), picks=True)
+        _requests(aggs_of("first(temp, true)"), picks=True)
     with pytest.raises(Ineligible, match="^max_by$"):
-        _requests(_aggs("max_by(temp)"), picks=True)
+        _requests(aggs_of("max_by(temp)"), picks=True)
     # a caller that does not promise the window's row order gets no picks
     for item in ("first(temp)", "max_by(temp, ts)"):
         with pytest.raises(Ineligible):
-            _requests(_aggs(item))
+            _requests(aggs_of(item))
     # a two-lane decimal payload or order key
     for item in ("first(serial * 1.5)", "max_by(serial, serial * 1.5)", "min_by(serial * 1.5, y3)"):
         with pytest.raises(Ineligible, match="argument type"):
-            _layout(_aggs(item))
-    _r, L = _layout(_aggs("COUNT(*)", "SUM(y3)", "MIN(y3)", "AVG(hum)"))
+            _layout(aggs_of(item))
+    _r, L = _layout(aggs_of("COUNT(*)", "SUM(y3)", "MIN(y3)", "AVG(hum)"))
     assert "pickdesc" not in L and "pickargs" not in L and not {6, 7} & set(L["line_ops"])
     assert L["fin"] == [(0, 8, -1), (1, 0, 9), (9, 16, 9), (3, 11, 10)]
 
@@ -326,8 +233,8 @@ def test_refusals_and_layouts_without_picks():
 def test_cpu_stream_takes_the_other_paths():
     """On a CPU device first / last are answered from pane partials and max_by / min_by by the generic evaluator: no
     dense state, and the streams' results equal the oracle (which guards the helpers)."""
-    store = new_store()
-    run_stream(small_stream(8, whole=False), [Q_MIXED, Q_TYPES], torch.device("cpu"), store)
+    store = new_store(5)
+    run_stream(small_stream(8, whole=False), [Q_MIXED, Q_TYPES], torch.device("cpu"), store, BITS)
     assert not dense_states(store)
 
 
@@ -335,8 +242,8 @@ def test_cpu_stream_takes_the_other_paths():
 @pytest.mark.gpu
 def test_mixed_statement(gpu):
     """4 groups, 40 rows per batch, a 5-s window, 12 batches: the four picks beside COUNT(*), AVG and MAX(y)."""
-    store = new_store()
-    run_stream(small_stream(12), [Q_MIXED], gpu, store)
+    store = new_store(5)
+    run_stream(small_stream(12), [Q_MIXED], gpu, store, BITS)
     d, = on_the_ring(store)
     assert len(d.layout["pickargs"][0]) == 4 and d.pickdesc_dev is not None
 
@@ -346,16 +253,16 @@ def test_ties_inside_and_across_panes(gpu):
     """``y3`` has three values, so every group ties inside a pane and across panes, and ``serial`` shows which row was
     picked.  The window's newest pane is listed first (``newest_first``): a group's extreme ``y3`` is seen both there
     and in older panes, and then the newest pane's row must win although its key is the largest."""
-    store = new_store()
+    store = new_store(5)
     seen = {"newest": 0, "older": 0}
 
-    def each(b, q, rows, view):
+    def each(b, q, rows, view, table):
         first = view.pieces()[0][0].key // S - 100 if view.pieces() else -1
         for r in rows:
             if r["deviceId"] < 900 and r["mx"] is not None:
                 seen["newest" if r["mx"] // 100_000 == first else "older"] += 1
 
-    run_stream(small_stream(12), [Q_TIES], gpu, store, each, reorder=newest_first)
+    run_stream(small_stream(12), [Q_TIES], gpu, store, BITS, each, reorder=newest_first)
     on_the_ring(store)
     assert seen["newest"] > 12 and seen["older"] > 0, seen
 
@@ -364,12 +271,12 @@ def test_ties_inside_and_across_panes(gpu):
 def test_nulls(gpu):
     """Rows with NULL y are present and never win; device 900 has no non-NULL y (NULL max_by / min_by, but a first and
     a last); winning rows and first / last rows whose x is NULL give NULL."""
-    store = new_store()
+    store = new_store(5)
     q = ("SELECT deviceId, COUNT(*) AS c, COUNT(y3) AS ny, max_by(temp, y3) AS mt, min_by(flag, y3) AS nf, "
          "first(temp) AS ft, last(flag) AS lf, first(serial) AS f FROM W GROUP BY deviceId")
     seen = {"allnull": 0, "nullx": 0, "nullfirst": 0}
 
-    def each(b, _q, rows, view):
+    def each(b, _q, rows, view, table):
         for r in rows:
             if r["deviceId"] == 900:
                 assert r["ny"] == 0 and r["mt"] is None and r["nf"] is None and r["f"] is not None, r
@@ -379,7 +286,7 @@ def test_nulls(gpu):
             if r["ft"] is None or r["lf"] is None:
                 seen["nullfirst"] += 1
 
-    run_stream(small_stream(12), [q], gpu, store, each)
+    run_stream(small_stream(12), [q], gpu, store, BITS, each)
     on_the_ring(store)
     assert seen["allnull"] >= 10 and seen["nullx"] > 0 and seen["nullfirst"] > 0, seen
 
@@ -388,13 +295,13 @@ def test_nulls(gpu):
 def test_clipped_panes(gpu):
     """Event times spread over the whole batch second: the panes at the window's edges are partly inside it and are
     accumulated into scratch slots, which take their panes' places in the window's order."""
-    store = new_store()
+    store = new_store(5)
     seen = {"clipped": 0}
 
-    def each(b, q, rows, view):
+    def each(b, q, rows, view, table):
         seen["clipped"] += sum(1 for _p, full in view.pieces() if not full)
 
-    run_stream(small_stream(12, whole=False), [Q_MIXED], gpu, store, each)
+    run_stream(small_stream(12, whole=False), [Q_MIXED], gpu, store, BITS, each)
     on_the_ring(store)
     assert seen["clipped"] >= 10, seen
 
@@ -406,10 +313,10 @@ def test_blocks_form_and_expire(gpu, order):
     first: complete 16-pane blocks are pre-combined where their members stand together in the window's order — never
     the block whose newest member stands first, away from the others — and expire.  The run includes the batches in
     which the newest pane completes a block."""
-    store = new_store(win=40)
+    store = new_store(40)
     seen = {"blocks": set(), "most": 0}
 
-    def each(b, q, rows, view):
+    def each(b, q, rows, view, table):
         if not dense_states(store):                 # (the watermark keeps the first windows empty)
             return
         d = only_state(store)
@@ -417,7 +324,8 @@ def test_blocks_form_and_expire(gpu, order):
         seen["most"] = max(seen["most"], len(d.blocks))
         seen["now"] = set(d.blocks)
 
-    run_stream(small_stream(66), [Q_TIES], gpu, store, each, reorder=newest_first if order == "newest" else None)
+    run_stream(small_stream(66), [Q_TIES], gpu, store, BITS, each,
+               reorder=newest_first if order == "newest" else None)
     on_the_ring(store)
     assert len(seen["blocks"]) >= 3 and seen["most"] >= 2 and seen["blocks"] - seen["now"], seen
 
@@ -427,38 +335,22 @@ def test_straddles_the_lds_bound(gpu, monkeypatch):
     """About 1,500 groups — ids on both sides of the pick pass's LDS bound — and 3,000 rows per batch."""
     from dxa.engine import window_dense
     from dxa.ops import native as N
-    import numpy as np
     L = N.lib().dxa_win_m2_lds_groups()
     assert 0 < L < 1500
     if 3000 > window_dense.DENSE_GROUPS:
         monkeypatch.setattr(window_dense, "DENSE_GROUPS", 4096)
-    rng = np.random.default_rng(37)
-    stream = []
-    for b in range(8):
-        ids = np.repeat(np.arange(1500), 2)
-        rng.shuffle(ids)
-        stream.append(((100 + b) * S, batch(rng, b, (100 + b) * S, ids, S - 1)))
-    store = new_store()
-    run_stream(stream, [Q_TIES], gpu, store)
+    store = new_store(5)
+    run_stream(two_rows_per_id_stream(numbered, 8, 1500), [Q_TIES], gpu, store, BITS)
     on_the_ring(store)
 
 
 @pytest.mark.gpu
 def test_rebuild_moves_the_pick_words(gpu, monkeypatch):
-    """Ids drift through a 16-id dictionary that grows to 64 at most (the patching of
-    tests/test_window_dense_churn.py): every rebuild renumbers the rank, payload and validity words with the others."""
-    from dxa.engine import window_dense
-    import numpy as np
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS", 16)
-    monkeypatch.setattr(window_dense, "DENSE_GROUPS_MAX", 64)
-    monkeypatch.setattr(window_dense, "BLOCK", 2)
-    rng = np.random.default_rng(23)
-    stream = []
-    for b in range(30):
-        ids = rng.integers(4 * b, 4 * b + 12, 120)
-        stream.append(((100 + b) * S, batch(rng, b, (100 + b) * S, ids, S - 1)))
-    store = new_store()
-    run_stream(stream, [Q_MIXED], gpu, store)
+    """Ids drift through a 16-id dictionary that grows to 64 at most: every rebuild renumbers the rank, payload and
+    validity words with the others."""
+    set_caps(monkeypatch, 16, 64, block=2)
+    store = new_store(5)
+    run_stream(churn_stream(numbered, 30, rows=120), [Q_MIXED], gpu, store, BITS)
     d, = on_the_ring(store)
     assert d.rebuilds > 0 and d.gcap <= 64
 
@@ -467,17 +359,17 @@ def test_rebuild_moves_the_pick_words(gpu, monkeypatch):
 def test_where_removes_the_would_be_winners(gpu):
     """Every device's first row has the largest y and its last row the smallest, and WHERE removes both: they go to
     the dump row and win nothing."""
-    store = new_store()
+    store = new_store(5)
     seen = {"bait": 0}
 
-    def each(b, q, rows, view):
-        mat = Table(view.names, view.columns, view.length, view._device).to("cpu")
+    def each(b, q, rows, view, table):
+        mat = materialised(view)
         baits = {s for s, k in zip(mat.column("serial").to_pylist(), mat.column("keep").to_pylist()) if k == 0}
         seen["bait"] += len(baits)
         for r in rows:
             assert not {r["f"], r["l"], r["mx"], r["mn"]} & baits, r
 
-    run_stream(small_stream(12, bait=True), [Q_WHERE], gpu, store, each)
+    run_stream(small_stream(12, bait=True), [Q_WHERE], gpu, store, BITS, each)
     on_the_ring(store)
     assert seen["bait"] > 50, seen
 
@@ -486,10 +378,10 @@ def test_where_removes_the_would_be_winners(gpu):
 def test_argument_types(gpu):
     """x: double (NaN, -0.0), float, boolean, timestamp, decimal(18,2); y: double (NaN the largest; -0.0 and 0.0 tie,
     and the first row wins), timestamp, decimal(10,1).  The results have x's type."""
-    store = new_store()
+    store = new_store(5)
     seen = {"nan": 0, "negzero": 0}
 
-    def each(b, q, rows, view):
+    def each(b, q, rows, view, table):
         for r in rows:
             for nm in ("ft", "xt", "nt"):
                 v = r[nm]
@@ -497,7 +389,7 @@ def test_argument_types(gpu):
                     seen["nan"] += math.isnan(v)
                     seen["negzero"] += v == 0.0 and math.copysign(1.0, v) < 0
 
-    run_stream(small_stream(12, whole=False), [Q_TYPES], gpu, store, each)
+    run_stream(small_stream(12, whole=False), [Q_TYPES], gpu, store, BITS, each)
     d, = on_the_ring(store)
     assert seen["nan"] > 0 and seen["negzero"] > 0, seen
     dts = [str(p[4]) for p in d.layout["plan"]]
@@ -508,8 +400,8 @@ def test_argument_types(gpu):
 def test_string_payload_falls_back(gpu):
     """first(name) of a string: the state is disabled with "argument type" and the paned path answers; max_by(name, y)
     is disabled likewise and the generic path answers.  Both equal the oracle."""
-    store = new_store()
-    run_stream(small_stream(8), [Q_STR, Q_STR_BY], gpu, store)
+    store = new_store(5)
+    run_stream(small_stream(8), [Q_STR, Q_STR_BY], gpu, store, BITS)
     states = list(dense_states(store).values())
     assert len(states) == 2
     for d in states:
@@ -523,27 +415,15 @@ def test_one_pick_pass_per_accumulated_pane(gpu, monkeypatch, q, picks):
     entry points tests/test_window_dense_comoments.py pins and never ``dxa_win_pick``; a pick statement calls it once
     per accumulated pane, right after the multi-aggregate."""
     from dxa.engine import window_dense
-    from launch_count import count_launches
     monkeypatch.setattr(window_dense, "BLOCK", 2)
-    store = new_store(win=6)
+    store = new_store(6)
     pane = ["dxa_win_insert_fused", "dxa_aggregate_multi", *["dxa_win_pick"] * picks]
     completed_seen = set()
-    for b, (T, tbl) in enumerate(small_stream(14)):
-        views, _ = store.process(tbl.to(gpu), T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        states = list(dense_states(store).values())
-        before = set(states[0].blocks) if states else set()
-        with count_launches() as log:
-            out = run_sql(q, cat, EvalContext(now_us=0, device=gpu))
-        assert_rows(rows_of(out), oracle(q, views["W"]), (b, q))
-        if b < 8:                                   # the watermark and the 6-pane window: full from batch 7 on
-            continue
+    # the watermark and the 6-pane window: full from batch 7 on
+    for b, native, completed in steady_state_launches(gpu, store, small_stream(14), q, BITS, 8):
         d, = on_the_ring(store)
         assert d.rebuilds == 0 and d.has_picks == bool(picks)
-        completed = len(set(d.blocks) - before)
         completed_seen.add(completed)
-        native = [nm for nm in log if nm.startswith("dxa_")]
         assert native == pane + ["dxa_win_combine_block"] * completed + ["dxa_win_answer"], (b, native)
     assert completed_seen == {0, 1}
     d = only_state(store)
@@ -552,28 +432,12 @@ def test_one_pick_pass_per_accumulated_pane(gpu, monkeypatch, q, picks):
 
 @pytest.mark.gpu
 def test_partials_at_world_size_one(gpu, monkeypatch):
-    """The N-rank form at world size 1 (the patching of tests/test_window_dense_decimal.py): for first / last the ring
-    hands ``merge_partials`` the state "v" of ``distagg._partials``, with V as its validity, and the merged result
-    equals the oracle."""
-    from dxa import parallel as P
-    from dxa.engine import distagg, window_dense
-    monkeypatch.setattr(P, "active", lambda: True)
-    monkeypatch.setattr(distagg, "exchange_partials", lambda partial, key_names, grouped: (partial, P.HASHED))
-    calls = {"n": 0}
-    real = window_dense.dense_partials
-
-    def counted(*a, **k):
-        got = real(*a, **k)
-        calls["n"] += got is not None
-        return got
-
-    monkeypatch.setattr(window_dense, "dense_partials", counted)
-
-    def prepare(view):
-        view.dist = P.PARTITIONED
-
-    store = new_store()
+    """The N-rank form at world size 1 (``as_partitioned_world_of_one``): for first / last the ring hands
+    ``merge_partials`` the state "v" of ``distagg._partials``, with V as its validity, and the merged result equals
+    the oracle."""
+    calls, prepare = as_partitioned_world_of_one(monkeypatch)
+    store = new_store(5)
     stream = small_stream(12, whole=False)
-    run_stream(stream, [Q_FIRST_LAST], gpu, store, prepare=prepare)
+    run_stream(stream, [Q_FIRST_LAST], gpu, store, BITS, prepare=prepare)
     on_the_ring(store)
     assert calls["n"] >= len(stream) - 4          # (the watermark keeps the first windows empty)

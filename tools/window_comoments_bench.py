@@ -18,25 +18,13 @@ only ``WindowStore``, ``run_sql`` and synthetic device batches, so the same file
 two statements re-group the materialised window every batch: ``dense`` false, no state at all).
 
     python tools/window_comoments_bench.py [--batches 160] [--rows 200000] [--panes 60]
-                                           [--runs grouped,few,variance,control]
+                                           [--runs grouped,few,variance,control] [--modes ring,fallback]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from window_bench import S, emit, lines, options, parse      # (first: it puts the repository on sys.path)
 
-import torch  # noqa: E402
-
-from dxa.engine.column import PrimColumn, Table  # noqa: E402
-from dxa.engine.expr import EvalContext  # noqa: E402
-from dxa.engine.query import Catalog, run_sql  # noqa: E402
-from dxa.engine.windows import TimeWindowConf, WindowStore  # noqa: E402
-
-S = 1_000_000
+from dxa.engine.column import PrimColumn, Table
 _NEW = "AVG(temp) AS av, corr(temp, hum) AS cr, skewness(temp) AS sk, kurtosis(temp) AS ku"
 SQL = {
     "grouped": f"SELECT deviceId, {_NEW} FROM W GROUP BY deviceId",
@@ -67,47 +55,10 @@ def batches(nb, rows, dev):
     return out
 
 
-def run(name, nb, rows, panes, tail, dev):
-    data = batches(nb, rows, dev)
-    store = WindowStore(TimeWindowConf({"W": panes * S}, True, "ts", 2 * S, panes * S, False))
-    ctx = EvalContext(now_us=0, device=dev)
-    events = [torch.cuda.Event(enable_timing=True) for _ in range(nb + 1)]
-    out_rows = 0
-    t0 = time.perf_counter()
-    events[0].record()
-    for b, (T, tbl) in enumerate(data):
-        views, _ = store.process(tbl, T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        out_rows = run_sql(SQL[name], cat, ctx).length
-        events[b + 1].record()
-    torch.cuda.synchronize(dev)
-    wall = time.perf_counter() - t0
-    per_batch = [events[b].elapsed_time(events[b + 1]) for b in range(nb)]
-    states = list(store.__dict__.get("_dense", {}).values())
-    st = states[0] if states else None
-    return {"run": name, "batches": nb, "rows_per_batch": rows, "panes": panes,
-            "median_ms_last": round(statistics.median(per_batch[-tail:]), 3),
-            "wall_s": round(wall, 3), "rows_last": out_rows,
-            "dense": bool(st is not None and not st.disabled),
-            "rebuilds": getattr(st, "rebuilds", None), "gcap": getattr(st, "gcap", None),
-            "disabled_reason": getattr(st, "disabled_reason", None)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, default=160)
-    ap.add_argument("--rows", type=int, default=200_000)
-    ap.add_argument("--panes", type=int, default=60)
-    ap.add_argument("--tail", type=int, default=100, help="batches at the end whose median is reported")
-    ap.add_argument("--runs", default="grouped,few,variance,control")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("window_comoments_bench.py measures on a GPU; none found")
-    dev = torch.device("cuda", 0)
-    for name in args.runs.split(","):
-        print(json.dumps(run(name, args.batches, args.rows, args.panes, min(args.tail, args.batches), dev)),
-              flush=True)
+    args, dev = parse(options(batches=160, rows=200_000, panes=60, tail=100, runs="grouped,few,variance,control"))
+    for line in lines(args, dev, SQL, lambda name: batches(args.batches, args.rows, dev)):
+        emit(line)
 
 
 if __name__ == "__main__":

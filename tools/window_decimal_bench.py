@@ -20,30 +20,21 @@ rows per batch over 10 K ids, 160 batches, and the statements
 * ``control``: ``AVG(temp)`` over the long itself.
 
 One JSON line per run: the median per-batch time of the last 100 batches (device events after each batch, read after
-a final synchronise) and whether a dense state answered.  This mode uses only ``WindowStore`` and ``run_sql``, so the
+a final synchronise), whether a dense state answered, and under ``path`` the ``--modes`` entry (ring or fallback; the
+line's ``mode`` is this script's own).  This mode uses only ``WindowStore`` and ``run_sql``, so the
 same file runs on older trees (where ``decimal`` is answered by the paned path: ``dense`` false, "argument type").
 
     python tools/window_decimal_bench.py --mode kernels [--rows 1000000] [--groups 16,100000]
-    python tools/window_decimal_bench.py --mode stream [--runs decimal,control]
+    python tools/window_decimal_bench.py --mode stream [--runs decimal,control] [--modes ring,fallback]
 """
-import argparse
 import ctypes
-import json
-import os
-import statistics
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
 
-import torch  # noqa: E402
+from window_bench import S, emit, lines, options, parse      # (first: it puts the repository on sys.path)
 
-from dxa.engine.column import PrimColumn, Table  # noqa: E402
-from dxa.engine.expr import EvalContext  # noqa: E402
-from dxa.engine.query import Catalog, run_sql  # noqa: E402
-from dxa.engine.windows import TimeWindowConf, WindowStore  # noqa: E402
+from dxa.engine.column import PrimColumn, Table
 
-S = 1_000_000
 SQL = {
     "decimal": "SELECT deviceId, AVG(temp * 1.8 + 32) AS av FROM W GROUP BY deviceId",
     "narrow": "SELECT deviceId, AVG(CAST(temp AS DECIMAL(18,2))) AS av FROM W GROUP BY deviceId",
@@ -125,54 +116,20 @@ def batches(nb, rows, dev):
     return out
 
 
-def stream(name, nb, rows, panes, tail, dev):
-    data = batches(nb, rows, dev)
-    store = WindowStore(TimeWindowConf({"W": panes * S}, True, "ts", 2 * S, panes * S, False))
-    ctx = EvalContext(now_us=0, device=dev)
-    events = [torch.cuda.Event(enable_timing=True) for _ in range(nb + 1)]
-    out_rows = 0
-    t0 = time.perf_counter()
-    events[0].record()
-    for b, (T, tbl) in enumerate(data):
-        views, _ = store.process(tbl, T, S)
-        cat = Catalog()
-        cat.register("W", views["W"])
-        out_rows = run_sql(SQL[name], cat, ctx).length
-        events[b + 1].record()
-    torch.cuda.synchronize(dev)
-    wall = time.perf_counter() - t0
-    per_batch = [events[b].elapsed_time(events[b + 1]) for b in range(nb)]
-    states = list(store.__dict__.get("_dense", {}).values())
-    st = states[0] if states else None
-    return {"mode": "stream", "run": name, "batches": nb, "rows_per_batch": rows, "panes": panes,
-            "median_ms_last": round(statistics.median(per_batch[-tail:]), 3), "wall_s": round(wall, 3),
-            "rows_last": out_rows, "dense": bool(st is not None and not st.disabled),
-            "disabled_reason": getattr(st, "disabled_reason", None)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
+    ap = options(batches=160, rows=None, panes=60, tail=100, runs="decimal,control")
     ap.add_argument("--mode", choices=("kernels", "stream"), required=True)
-    ap.add_argument("--rows", type=int, default=None, help="rows per pane (kernels: 1 M) or batch (stream: 200 K)")
     ap.add_argument("--groups", default="16,100000")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--batches", type=int, default=160)
-    ap.add_argument("--panes", type=int, default=60)
-    ap.add_argument("--tail", type=int, default=100, help="batches at the end whose median is reported")
-    ap.add_argument("--runs", default="decimal,control")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("window_decimal_bench.py measures on a GPU; none found")
-    dev = torch.device("cuda", 0)
+    args, dev = parse(ap)           # --rows: per pane (kernels: 1 M by default) or per batch (stream: 200 K)
     if args.mode == "kernels":
         for groups in map(int, args.groups.split(",")):
             for line in kernels(args.rows or 1_000_000, groups, args.warmup, args.reps, dev):
-                print(json.dumps(line), flush=True)
+                emit(line)
         return
-    for name in args.runs.split(","):
-        print(json.dumps(stream(name, args.batches, args.rows or 200_000, args.panes,
-                                min(args.tail, args.batches), dev)), flush=True)
+    for line in lines(args, dev, SQL, lambda name: batches(args.batches, args.rows or 200_000, dev)):
+        emit({"mode": "stream", "path": line.pop("mode"), **line})
 
 
 if __name__ == "__main__":
