@@ -167,12 +167,32 @@ validity taken from V, so N ranks merge them like the paned path; max_by / min_b
 distinct count they are tried here and nowhere else (``query._paned_aggregate``), and take the generic path when the
 ring declines, when the statement is not cacheable, or over a partitioned view at N ranks.
 
+**String arguments: COUNT / MIN / MAX** (a plain ``StrColumn``; up to ``MAX_STRING`` MIN / MAX jobs — argument and
+direction — per statement, "too many string arguments" beyond).  COUNT(x) reads the column's validity into the ordinary
+count slot.  The order of MIN / MAX is unsigned byte order of the UTF-8 bytes, a proper prefix first
+(``ops/sort.string_ranks``' and Python's).  A job is one whole line of the combine op ``MA_STRKEY`` = 8, for values of
+up to ``STR_WIDTH`` = 48 bytes: six words of the zero-padded bytes big-endian, each mapped to the signed order (^ 2^63),
+a length word and a spare; MIN complements every word; the identity of every word is INT64_MIN, below every value — ""
+included, whose length word is 0 (``pack_str_words`` / ``unpack_str_words`` are the host forms).  agg_multi sees the
+line as unused MAX words.  After the multi-aggregate ``dxa_win_strkey`` — one call per accumulated pane for all jobs —
+runs str_minmax.hip's arg-extreme kernel over the pane's rows (the pane's ids and WHERE mask) and a gather over the
+groups in use that checks the winning row index against [0, n) and writes its packed words.  The combine (one more
+``win_combine_kernel`` flag, instantiated only with a ``strdesc``) takes each word of the line from the slot whose
+7-word tuple is lexicographically greatest: a maximum over a total order, so block slots, scratch slots and rebuilds
+stay valid.  ``win_emit_kernel``'s kind ``F_STRW`` undoes a byte word's mapping and ``str_column_of`` builds the
+result column with tensor operations; the count word (shared with COUNT(x)) gives the validity.  A winning value of
+more than 48 bytes has no key: the gather sets status flag 8, which travels in the one status read, and the statement
+goes to the paned path for good ("argument too long"), where ``groupby.aggregate`` runs the same kernel per pane.  The
+partial states are ``distagg._partials``': "v" (a string column) and "cnt".  Everything else over a string, string
+payloads of row picks included, stays "argument type"; a pick's payload could reuse the line with its rank word as the
+source of the row index.
+
 **One answer, one plan entry per aggregate.**  Every layout is answered by the same call, ``dxa_win_answer``
 (combine, one distinct fold per pair state, keep, compaction, output rows), and its complete blocks are combined by
 ``dxa_win_combine_block``; the families differ only in what they hand over — the pair states' folds, ``m2desc``,
-``momdesc``, ``lodesc``, ``pickdesc``, each 0 when the layout has none — and the absent descriptors pick the
-``win_combine_kernel`` instantiation without that branch, so a layout without X issues the launches it would issue if
-X did not exist (tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate
+``momdesc``, ``lodesc``, ``pickdesc``, ``strdesc``, each 0 when the layout has none — and the absent descriptors pick
+the ``win_combine_kernel`` instantiation without that branch, so a layout without X issues the launches it would issue
+if X did not exist (tests/test_window_dense_comoments.py pins the sequences).  ``plan_layout`` describes an aggregate
 once, where its slots are chosen: its ``plan`` entry, its finishing recipe and its partial states, all in slot terms;
 one pass after packing turns slots into words.  Adding an aggregate means one arm there (and, for a new kind of word,
 its kernels).
@@ -188,9 +208,9 @@ import torch
 from ..ops import native as N
 from ..ops.groupby import (_DEC_KEY_MAX, _DEC_KEY_MIN, _DEC_SUM, _F_AVG, _F_CORR, _F_COUNT, _F_COVAR_POP, _F_COVAR_SAMP,
                            _F_DEC_AVG, _F_DEC_MM, _F_DEC_SUM, _F_F64, _F_F64_ORD, _F_HI, _F_I64, _F_KURT, _F_NOT,
-                           _F_SKEW, _F_SQRT, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64, _MA_LOKEY, _MA_M2,
-                           _MA_MAX, _MA_MOM, _MA_PICK_RANK, _MA_PICK_VAL, _MOM_CXY, _MOM_M3, _MOM_M4, _MV_COUNT,
-                           _MV_F64, _MV_F64_ORD, _MV_I64, _MV_NOT, _PICK_LAST, _PICK_USED)
+                           _F_SKEW, _F_SQRT, _F_STRW, _F_VAR_POP, _F_VAR_SAMP, _MA_ADD_F64, _MA_ADD_U64, _MA_LOKEY,
+                           _MA_M2, _MA_MAX, _MA_MOM, _MA_PICK_RANK, _MA_PICK_VAL, _MA_STRKEY, _MOM_CXY, _MOM_M3,
+                           _MOM_M4, _MV_COUNT, _MV_F64, _MV_F64_ORD, _MV_I64, _MV_NOT, _PICK_LAST, _PICK_USED)
 from ..ops.hashing import MAX_KEY_COLS, _KeyCols, key_cols
 from . import decimal as Dec
 from .column import ConstColumn, PrimColumn, StrColumn, materialize
@@ -211,9 +231,12 @@ MAX_DECIMAL = 8                   # decimal sum arguments plus two-lane decimal 
 SUM_PRECISION = 28                # SUM / AVG of decimal(p, s) is answered here for p up to this (``plan_layout``)
 MAX_PICK = 8                      # different rank jobs, and different payload jobs, of first / last / max_by / min_by
                                   # per statement (window_ring.hip kMaxPickJobs)
+MAX_STRING = 8                    # string MIN / MAX jobs (argument and direction) per statement (kMaxStrJobs)
+STR_WIDTH = 48                    # bytes of a string MIN / MAX value the ring holds (window_ring.hip kKeyWidth)
 _ANSWER = [N.c_p, N.c_i32, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p, N.c_p, N.c_p]    # ring … out_idx
-# m2desc, its host copy, momdesc, its host copy, lodesc, its host copy, pickdesc, its host copy (0: the layout has none)
-_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p]
+# m2desc, its host copy, momdesc, its host copy, lodesc, its host copy, pickdesc, its host copy, strdesc, its host copy
+# (0: the layout has none)
+_DESCS = [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_p]
 N.register_sigs({
     "dxa_win_sizes": [N.c_p],
     "dxa_win_emit_size": [],
@@ -225,6 +248,8 @@ N.register_sigs({
     "dxa_win_dec": [N.c_p, N.c_p],
     "dxa_win_pick_size": [],
     "dxa_win_pick": [N.c_p, N.c_p],
+    "dxa_win_strkey_size": [],
+    "dxa_win_strkey": [N.c_p, N.c_p],
     "dxa_win_init": [N.c_p, N.c_p, N.c_i64, N.c_p],
     "dxa_win_insert_fused": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_p, N.c_p, N.c_p],
     "dxa_win_m2": [N.c_p, N.c_p],
@@ -363,6 +388,18 @@ class _PickArgs(ctypes.Structure):
                 ("stride", ctypes.c_int32), ("nrank", ctypes.c_int32), ("nval", ctypes.c_int32)]
 
 
+class _StrJob(ctypes.Structure):
+    _fields_ = [("arena", ctypes.c_void_p), ("starts", ctypes.c_void_p), ("lens", ctypes.c_void_p),
+                ("valid", ctypes.c_void_p), ("line", ctypes.c_int32), ("min", ctypes.c_int32)]
+
+
+class _StrKeyArgs(ctypes.Structure):
+    _fields_ = [("a", _StrJob * MAX_STRING), ("gid", ctypes.c_void_p), ("keep", ctypes.c_void_p),
+                ("row", ctypes.c_void_p), ("scal", ctypes.c_void_p), ("best", ctypes.c_void_p), ("n", ctypes.c_int64),
+                ("gcap", ctypes.c_int32), ("stride", ctypes.c_int32), ("njobs", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
 _SIZES: Optional[List[int]] = None
 
 
@@ -378,13 +415,53 @@ def _sizes() -> List[int]:
                 N.lib().dxa_win_m2_size() != ctypes.sizeof(_M2Args) or \
                 N.lib().dxa_win_mom_size() != ctypes.sizeof(_MomArgs) or \
                 N.lib().dxa_win_dec_size() != ctypes.sizeof(_DecArgs) or \
-                N.lib().dxa_win_pick_size() != ctypes.sizeof(_PickArgs):
+                N.lib().dxa_win_pick_size() != ctypes.sizeof(_PickArgs) or \
+                N.lib().dxa_win_strkey_size() != ctypes.sizeof(_StrKeyArgs) or _SIZES[2] != STR_WIDTH:
             raise N.NativeError("window_ring.hip struct layout differs from window_dense.py")
     return _SIZES
 
 
 class Ineligible(Exception):
     """The statement (or this batch) is answered by the paned path."""
+
+
+_I64_MIN = -(1 << 63)
+
+
+def _signed(u: int) -> int:
+    return u - (1 << 64) if u >> 63 else u
+
+
+def pack_str_words(b: bytes, is_min: bool = False) -> tuple:
+    """The 7 order-key words (signed 64-bit integers) of a string MIN / MAX value of up to ``STR_WIDTH`` bytes, as
+    win_strkey_gather_kernel writes them: six words of the zero-padded bytes big-endian, each mapped to the signed
+    order (^ 2^63), and the length; every word complemented for MIN.  The tuple order of two values' words is the byte
+    order of the values (reversed for MIN), and every tuple is above the identity (INT64_MIN seven times)."""
+    assert len(b) <= STR_WIDTH
+    padded = b.ljust(STR_WIDTH, b"\0")
+    words = [_signed(int.from_bytes(padded[q:q + 8], "big") ^ 1 << 63) for q in range(0, STR_WIDTH, 8)] + [len(b)]
+    return tuple(~w for w in words) if is_min else tuple(words)
+
+
+def unpack_str_words(words, is_min: bool = False) -> Optional[bytes]:
+    """``pack_str_words`` undone; the identity ("no row") gives None."""
+    if all(w == _I64_MIN for w in words):
+        return None
+    words = [~w for w in words] if is_min else list(words)
+    raw = b"".join(((w ^ _I64_MIN) & (1 << 64) - 1).to_bytes(8, "big") for w in words[:6])
+    return raw[:words[6]]
+
+
+def str_column_of(words: List[torch.Tensor], lens: torch.Tensor, ok: torch.Tensor) -> StrColumn:
+    """The finished words of a string MIN / MAX (win_emit_kernel has undone the mapping: six rows of big-endian byte
+    words and a row of lengths, [groups] each) as a string column over a fresh arena of ``STR_WIDTH`` bytes per group.
+    Tensor operations only."""
+    n = int(lens.shape[0])
+    arena = torch.stack(words, dim=1).contiguous().view(torch.uint8).view(n, len(words), 8).flip(2).reshape(-1)
+    starts = torch.arange(n, dtype=torch.int64, device=lens.device) * STR_WIDTH
+    c = StrColumn(arena, starts, torch.where(ok, lens, torch.zeros_like(lens)).to(torch.int32), ok)
+    c.max_len = STR_WIDTH
+    return c
 
 
 def _requests(aggs: Dict, picks: bool = False, distinct_sums: bool = False):
@@ -547,7 +624,16 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     ``MA_MAX`` slot of y.  ``pickdesc`` (per word of those lines: R word | (K word + 1) << 8 | last << 16 | in use <<
     17) is win_combine_kernel's, ``pickargs`` = (rank jobs [(K argument key or None, K value kind, K word or -1, R
     word, last)], payload jobs [(x key, R word, P word, V word, last)]) dxa_win_pick's, ``pick_x`` maps a pick's agg key
-    to its payload argument.  All three are absent from a layout without picks."""
+    to its payload argument.  All three are absent from a layout without picks.
+
+    MIN / MAX of a string argument (``arg_types`` entry ("string", False)): one whole ``MA_STRKEY`` line per argument
+    and direction — eight slots of value kind -1: six byte words, the length word, a spare — and the argument's
+    ordinary count slot, which COUNT of the same argument shares.  Seven ``fin`` rows (``_F_STRW`` for the byte words,
+    ``_F_I64`` for the length; ``_F_NOT`` for MIN), a ``plan`` entry of kind "str" and the partial states "v" (the seven
+    recipes) and "cnt".  ``strdesc`` (per word of such a line its place in the tuple + 1) is win_combine_kernel's,
+    ``strargs`` [(argument key, is MIN, first word)] dxa_win_strkey's; both are absent from a layout without string
+    lines.  More than ``MAX_STRING`` jobs: "too many string arguments".  COUNT of a string reads its validity like any
+    count; every other aggregate over one is "argument type" (``DenseWindow.accumulate``)."""
     # accumulator slots, packed into 8-word lines of one atomic kind (as groupby.aggregate_many packs them)
     slots, keyed = [], {}
 
@@ -569,6 +655,7 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
     pick_ranks = {}                 # R slot → (K slot's argument key or None, its value kind, K slot or None, last)
     pick_vals = {}                  # P slot → (x key, R slot, V slot, last)
     pick_x = {}                     # agg key of a pick → its payload argument's key
+    str_jobs = {}                   # (func, argument key) of a string MIN / MAX → (argument key, is MIN, its 8 slots)
 
     def agg(ak, kind, s, c, dt, fkind, states, ops=(), f64=None):
         """One aggregate, described once and in slot terms (mapped to words after packing): its ``plan`` entry, its
@@ -688,9 +775,23 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         if func in (*_MOMENTS, *_VARIANCE, "sum") and not numeric(dtype):
             raise Ineligible(f"{func} type")
         dec = dtype if is_decimal(dtype) else None
+        if dtype == "string" and func not in ("count", "min", "max"):
+            raise Ineligible("argument type")
         cnt = slot(("count", ck), _MV_COUNT, _MA_ADD_F64)
         if func == "count":
             agg(ak, "count", cnt, None, None, _F_COUNT, {"cnt": count_of(cnt)})
+        elif dtype == "string":
+            # MIN / MAX of a string: one whole line is its order key (six byte words, the length, a spare), which
+            # agg_multi leaves at INT64_MIN (value kind -1) and dxa_win_strkey fills
+            inv = func == "min"
+            job = str_jobs.get((func, ck))
+            if job is None:
+                job = str_jobs[(func, ck)] = (ck, inv, [slot(("strk", (func, ck), q), -1, _MA_STRKEY)
+                                                        for q in range(8)])
+            w = job[2]
+            flip = _F_NOT if inv else 0
+            recipes = [(_F_STRW | flip, w[q], cnt) for q in range(6)] + [(_F_I64 | flip, w[6], cnt)]
+            agg(ak, "str", w[0], cnt, "string", recipes, {"v": recipes, "cnt": count_of(cnt)}, f64=False)
         elif func in _MOMENTS or func in _VARIANCE:
             # (n, Σx, M2) of the argument: the count and sum words AVG of the same argument uses, and one M2 word
             # in a line only window_ring.hip combines (MA_M2); agg_multi leaves it at 0.0 (value kind -1) and
@@ -760,7 +861,10 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
         raise Ineligible("too many decimal arguments")
     if len(pick_ranks) > MAX_PICK or len(pick_vals) > MAX_PICK:
         raise Ineligible("too many pick arguments")
-    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM, _MA_LOKEY, _MA_PICK_RANK, _MA_PICK_VAL):
+    if len(str_jobs) > MAX_STRING:
+        raise Ineligible("too many string arguments")
+    for op in (_MA_ADD_U64, _MA_ADD_F64, _MA_MAX, _MA_M2, _MA_MOM, _MA_LOKEY, _MA_PICK_RANK, _MA_PICK_VAL,
+               _MA_STRKEY):
         mine = [i for i, sl in enumerate(slots) if sl[2] == op]
         for k in range(0, len(mine), 8):
             chunk = mine[k:k + 8]
@@ -821,6 +925,17 @@ def plan_layout(reqs, arg_types: Dict) -> Dict:
                             for r, (yk, kk, ks, last) in pick_ranks.items()],
                            [(xk, where[r], where[pv], where[vv], int(last))
                             for pv, (xk, r, vv, last) in pick_vals.items()])
+    if str_jobs:
+        # per word of a string line: its place in the line's 7-word tuple + 1 (win_combine_kernel; 0: the spare word);
+        # the jobs [(argument key, is MIN, the line's first word)] of dxa_win_strkey.  A job's eight slots are created
+        # together, so they fill exactly one line
+        strdesc = [0] * stride
+        for ck, inv, w in str_jobs.values():
+            assert where[w[0]] % 8 == 0 and all(where[w[q]] == where[w[0]] + q for q in range(8))
+            for q in range(7):
+                strdesc[where[w[q]]] = q + 1
+        out["strdesc"] = strdesc
+        out["strargs"] = [(ck, inv, where[w[0]]) for ck, inv, w in str_jobs.values()]
     if mom_of:
         # per op-4 word: kind << 24 | the words it reads, 6 bits each (win_combine_kernel); per argument or pair the
         # words of its job in the pane's moment pass (win_mom_kernel)
@@ -975,6 +1090,7 @@ class DenseWindow:
         self.momdesc_t = self.momdesc_dev = None        # with op-4 lines: its M3 / M4 / Cxy descriptor
         self.lodesc_t = self.lodesc_dev = None          # with low-key lines (two-lane decimal MIN / MAX): the high words
         self.pickdesc_t = self.pickdesc_dev = None      # with row picks: the R and K word of each pick word
+        self.strdesc_t = self.strdesc_dev = None        # with string MIN / MAX lines: each word's place in its tuple
         # row picks combine slots by their place in the window's row order (``_enqueue``)
         self.has_picks = any(func in _PICKS for _, func, _arg in reqs)
         self.slot_of: Dict[int, tuple] = {}     # pane key → (ring slot, the pane, block id, pane key)
@@ -1053,7 +1169,7 @@ class DenseWindow:
             self.keys, self.dictcols = self._alloc_keys(kinds, self.gcap)
         except torch.cuda.OutOfMemoryError:
             raise Ineligible("memory") from None
-        types = {k: (c.dtype, c.data.dtype == torch.float64) for k, c in args.items()}
+        types = {k: (c.dtype, isinstance(c, PrimColumn) and c.data.dtype == torch.float64) for k, c in args.items()}
         for _, func, arg in self.reqs:
             if func in ("dsum", "davg"):        # the distinct sums' arguments, as ``_distinct_arg`` widened them
                 c = dargs[arg.key()][0]
@@ -1061,21 +1177,26 @@ class DenseWindow:
         L = plan_layout(self.reqs, types)
         L["pspec_of"] = self._partial_spec
         # payload arguments stored as float32: their picks are kept as doubles and narrowed again in ``_finals``
-        self.f32_args = {k for k, c in args.items() if c.data.dtype == torch.float32}
+        self.f32_args = {k for k, c in args.items() if isinstance(c, PrimColumn) and c.data.dtype == torch.float32}
         self.stride = L["stride"]
         self.layout = L
         # agg_multi (host ``line_ops_t``) sees an M2 line as an f64 add line of unused slots, so every pane starts
         # its M2 words at 0.0; the ring kernels (``line_ops_dev``) see MA_M2
         # and a low-key line as a max line of unused slots, so every pane starts its low key words at INT64_MIN; so do
-        # a pick's rank words, and its payload and validity words start at 0 as unused u64 add words
+        # a pick's rank words and the words of a string order key, and a pick's payload and validity words start at 0 as
+        # unused u64 add words
         host_op = {_MA_M2: _MA_ADD_F64, _MA_MOM: _MA_ADD_F64, _MA_LOKEY: _MA_MAX, _MA_PICK_RANK: _MA_MAX,
-                   _MA_PICK_VAL: _MA_ADD_U64}
+                   _MA_PICK_VAL: _MA_ADD_U64, _MA_STRKEY: _MA_MAX}
         self.line_ops_t = torch.tensor([host_op.get(op, op) for op in L["line_ops"]], dtype=torch.int32)
         self.line_ops_dev = torch.tensor(L["line_ops"], dtype=torch.int32).to(self.device)
         self.m2desc_t = self.m2desc_dev = None
         self.momdesc_t = self.momdesc_dev = None
         self.lodesc_t = self.lodesc_dev = None
         self.pickdesc_t = self.pickdesc_dev = None
+        self.strdesc_t = self.strdesc_dev = None
+        if "strdesc" in L:
+            self.strdesc_t = torch.tensor(L["strdesc"], dtype=torch.int32)
+            self.strdesc_dev = self.strdesc_t.to(self.device)
         if "pickdesc" in L:
             self.pickdesc_t = torch.tensor(L["pickdesc"], dtype=torch.int32)
             self.pickdesc_dev = self.pickdesc_t.to(self.device)
@@ -1220,13 +1341,19 @@ class DenseWindow:
                                                 for a in (arg if isinstance(arg, tuple) else (arg,))]
                 continue
             for a in arg if isinstance(arg, tuple) else () if arg is None else (arg,):
-                if a.key() in args:
-                    continue
-                c = evaluate(a, scope, ctx)
-                if isinstance(c, ConstColumn):
-                    c = c.materialize()
+                # an argument evaluated for an earlier aggregate is checked again against this one's func: COUNT(name)
+                # admits a string column that SUM(name) of the same statement must still refuse
+                c = args.get(a.key())
+                if c is None:
+                    c = evaluate(a, scope, ctx)
+                    if isinstance(c, ConstColumn):
+                        c = c.materialize()
+                if type(c) is StrColumn and c.dtype == "string":
+                    # a plain string column: COUNT reads its validity, MIN / MAX keep its order key; nothing else
+                    if func not in ("count", "min", "max"):
+                        raise Ineligible("argument type")
                 # a decimal argument keeps its storage: one int64 lane per row, or two for more than 18 digits
-                if not isinstance(c, PrimColumn) or \
+                elif not isinstance(c, PrimColumn) or \
                         c.data.dim() != (2 if is_decimal(c.dtype) and not c.dtype.narrow else 1):
                     raise Ineligible("argument type")
                 args[a.key()] = c
@@ -1244,12 +1371,14 @@ class DenseWindow:
                     x.valid.to(torch.bool) & y.valid.to(torch.bool)
                 kx, ky = pair_keys(*arg)
                 args[kx], args[ky] = PrimColumn(x.dtype, x.data, both), PrimColumn(y.dtype, y.data, both)
-        dec_types = {k: str(c.dtype) for k, c in args.items() if is_decimal(c.dtype)}
+        # the arguments whose type shapes the layout: decimals (their words and win_dec_kernel's lanes follow the type)
+        # and strings (their MIN / MAX have lines of their own)
+        shaping_types = {k: str(c.dtype) for k, c in args.items() if is_decimal(c.dtype) or isinstance(c, StrColumn)}
         if self.layout is None:
             self._build_layout(keys, args, dargs)
-            self.dec_types = dec_types
+            self.shaping_types = shaping_types
         else:
-            if dec_types != self.dec_types:        # the layout's words and win_dec_kernel's lanes follow the types
+            if shaping_types != self.shaping_types:
                 raise Ineligible("argument types changed")
             for (dt, kind, *_), k in zip(self.keys, keys):
                 if (kind == 2) != isinstance(k, StrColumn) or str(dt) != str(k.dtype):
@@ -1370,16 +1499,34 @@ class DenseWindow:
             m.gid, m.row, m.scal, m.n = gid.data_ptr(), ring_ptr, self.scal.data_ptr(), n
             m.gcap, m.stride, m.nrank, m.nval = self.gcap, self.stride, len(ranks), len(vals)
             N.call("dxa_win_pick", ctypes.addressof(m), st)
+        if L.get("strargs") and n > 0:
+            # the string pass: per job the pane's winning row per group (str_minmax.hip, under the pane's ids and WHERE
+            # mask), then every job's packed order key into its line, all jobs of the statement in one call
+            m = _StrKeyArgs()
+            jobs = L["strargs"]
+            best = torch.empty((len(jobs), self.gcap), dtype=torch.int64, device=dev)
+            for k, (ck, inv, line) in enumerate(jobs):
+                c = args[ck]
+                v = N.u8(c.valid)
+                parts = (c.arena, c.starts.contiguous(), c.lens.contiguous(), None if v is None else v.contiguous())
+                hold.append(parts)
+                m.a[k] = _StrJob(*(N.ptr(t) or None for t in parts), line, int(inv))
+            hold.append(best)
+            m.gid, m.keep, m.row, m.scal = gid.data_ptr(), N.ptr(keep) or None, ring_ptr, self.scal.data_ptr()
+            m.best, m.n = best.data_ptr(), n
+            m.gcap, m.stride, m.njobs = self.gcap, self.stride, len(jobs)
+            N.call("dxa_win_strkey", ctypes.addressof(m), st)
         for ps in self.pairs:
             ps.insert(gid, n, dargs[ps.arg_key], slot_idx, st)
         del hold
 
     def _descs(self):
         """The combine's descriptors for ``dxa_win_answer`` / ``dxa_win_combine_block``: ``m2desc`` on the device and
-        on the host, ``momdesc``, ``lodesc`` and ``pickdesc`` likewise; 0 where the layout has none, which picks the
-        combine without that branch."""
+        on the host, ``momdesc``, ``lodesc``, ``pickdesc`` and ``strdesc`` likewise; 0 where the layout has none, which
+        picks the combine without that branch."""
         return (N.ptr(self.m2desc_dev), N.ptr(self.m2desc_t), N.ptr(self.momdesc_dev), N.ptr(self.momdesc_t),
-                N.ptr(self.lodesc_dev), N.ptr(self.lodesc_t), N.ptr(self.pickdesc_dev), N.ptr(self.pickdesc_t))
+                N.ptr(self.lodesc_dev), N.ptr(self.lodesc_t), N.ptr(self.pickdesc_dev), N.ptr(self.pickdesc_t),
+                N.ptr(self.strdesc_dev), N.ptr(self.strdesc_t))
 
     def _second_pass(self, m, nargs: int, gid: torch.Tensor, ring_ptr: int, n: int) -> int:
         """The fields ``_M2Args`` and ``_MomArgs`` share, after their jobs: the pane's group ids and ring slot → the
@@ -1463,6 +1610,8 @@ class DenseWindow:
     def _finish(self, status, bufs, fin, partial_proto):
         L = self.layout
         ng_all, bad, nout = status[:3]
+        # (the device's flag 8, "a winning string too long for its line", is 16 here: 8 is a pair dictionary's "full")
+        bad = (bad & 7) | (16 if bad & 8 else 0)
         for k, ps in enumerate(self.pairs):
             # a pair dictionary's collision / over-long value joins the outer flags; its "full" is flag 8 here
             pflags = status[4 + 4 * k + 1]
@@ -1471,8 +1620,8 @@ class DenseWindow:
         self.bad = bad
         if bad:
             # full dictionaries and nothing else: rebuilt before the next answer (dense_answer); a collision or an
-            # over-long key (never cleared on the device) sends the statement to the paned path for good
-            self.rebuild_pending = not bad & 5
+            # over-long key or string value (never cleared on the device) sends the statement to the paned path for good
+            self.rebuild_pending = not bad & (5 | 16)
             return None
         self.dirty = []
         okey, olen, ovalid, dst, dvalid = bufs
@@ -1506,9 +1655,11 @@ class DenseWindow:
         lo alone for up to 18 digits, else [n, 2]."""
         L = self.layout
         finals = {}
-        for (ak, _kind, _s, c, dt), f64, (r0, nr) in zip(L["plan"], L["as_f64"], L["rows"]):
+        for (ak, kind, _s, c, dt), f64, (r0, nr) in zip(L["plan"], L["as_f64"], L["rows"]):
             v, ok = cols[r0]
-            if nr == 2:
+            if kind == "str":   # a string MIN / MAX: six byte words and the length
+                finals[ak] = str_column_of([cols[r0 + q][0] for q in range(6)], cols[r0 + 6][0], ok)
+            elif nr == 2:
                 finals[ak] = PrimColumn(dt, Dec.pack(cols[r0 + 1][0], v, dt), ok)
             elif c is None:
                 finals[ak] = PrimColumn("long", v)
@@ -1550,20 +1701,26 @@ class DenseWindow:
                 f = L["pfin"].get(ak, {}).get(suffix)
                 if f is None:
                     raise Ineligible(f"partial {suffix}")
-                out.extend(f if isinstance(f, list) else [f])      # (a 128-bit decimal state: two rows)
+                out.extend(f if isinstance(f, list) else [f])      # (a 128-bit decimal state: two rows; a string: 7)
         return out
 
     def _partials(self, cols, out_keys, nout, proto, pplan, key_names):
         """This rank's kept groups as a partial table shaped like ``proto`` (column names, types, order)."""
         from .column import Table
         got = {nm: k for nm, k in zip(key_names, out_keys)}
+        kind_of = {p[0]: p[1] for p in self.layout["plan"]}
         j = 0
         for ak, entries in pplan.items():
             for nm, suffix, _op in entries:
                 like = proto.column(nm)
                 v, ok = cols[j]
                 j += 1
-                if isinstance(self.layout["pfin"][ak][suffix], list):
+                state = self.layout["pfin"][ak][suffix]
+                if kind_of[ak] == "str" and suffix == "v":
+                    # a string MIN / MAX value: six byte words and the length
+                    got[nm] = str_column_of([v, *(cols[j + q][0] for q in range(5))], cols[j + 5][0], ok)
+                    j += 6
+                elif isinstance(state, list):
                     # a 128-bit decimal state (lo, hi) as the prototype's type stores it
                     got[nm] = PrimColumn(like.dtype, Dec.pack(cols[j][0], v, like.dtype), ok)
                     j += 1
@@ -1685,8 +1842,8 @@ def dense_answer(t, sel, alias: str, ctx, items, aggs: Dict, fp: str, partial_pr
 
 def _flag_reason(bad: int) -> str:
     # an over-long key is stored with length 0, so later rows of that key also compare unequal (flag 1): 4 first
-    return "key too long" if bad & 4 else "hash collision" if bad & 1 else "dictionary full" if bad & 2 or not bad \
-        else "pair dictionary full"
+    return "key too long" if bad & 4 else "hash collision" if bad & 1 else "argument too long" if bad & 16 else \
+        "dictionary full" if bad & 2 or not bad else "pair dictionary full"
 
 
 def _disable(state, reason: str) -> None:

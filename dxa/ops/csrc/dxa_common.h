@@ -16,6 +16,10 @@ constexpr uint64_t kSeed = 0x5bd1e9955bd1e995ull;
 constexpr uint64_t kGold = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t kNullHash = 0x6e756c6c6e756c6cull;   // "nullnull"
 constexpr uint64_t kEmpty = 0xFFFFFFFFFFFFFFFFull;      // empty hash-table slot
+// Group ids below this go through a per-workgroup LDS array in the passes that put every row of a group on one word
+// (window_ring.hip's second passes, str_minmax.hip); the others go straight to global memory.  One constant, so a
+// test that straddles it (dxa_win_m2_lds_groups) straddles the bound of every such kernel.
+constexpr int kLdsGroupIds = 1024;
 
 __host__ __device__ __forceinline__ uint64_t fmix64(uint64_t x) {
   x ^= x >> 33;

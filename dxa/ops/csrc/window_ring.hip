@@ -37,10 +37,14 @@
 // AVG, divides it exactly with HALF_UP rounding); MIN / MAX of a two-lane decimal keep a two-word order key, the hi
 // word an ordinary MA_MAX word and the lo word in a line of the combine op MA_LOKEY (described by ``lodesc``).
 // Every layout goes through the same two host entry points, dxa_win_answer (steps 3-5) and dxa_win_combine_block; the
-// descriptors a layout passes (none, m2desc, m2desc + momdesc; with or without lodesc; with or without pickdesc) pick
+// descriptors a layout passes (none, m2desc, m2desc + momdesc; with or without lodesc; with or without pickdesc; with
+// or without strdesc) pick
 // the win_combine_kernel instantiation.
 // first / last / max_by / min_by keep a row pick per pane and group (a rank word, the picked row's value and its
 // validity; win_pick_kernel and win_pick_gather_kernel fill them) and slots combine by their place in the window.
+// MIN / MAX over a string argument keep the winning value's order key — a whole line of 8 words — per pane and group
+// (dxa_win_strkey: str_minmax.hip's arg-extreme kernel, then win_strkey_gather_kernel) and slots combine by the
+// greatest key tuple (``strdesc``).
 // So a batch costs one pane's aggregation plus a (groups × window panes) combine of L2/HBM-resident rows, instead of
 // re-grouping ~40 partial tables (the previous paned path), and one synchronising read instead of three.
 #include "dxa_common.h"
@@ -79,6 +83,15 @@ enum : int32_t { MA_LOKEY = 5 };
 // slots are combined by their place in the ``slots`` array (the window's row order), see win_combine_kernel.
 // agg_multi sees both kinds of line as unused words (INT64_MIN and 0).
 enum : int32_t { MA_PICK_RANK = 6, MA_PICK_VAL = 7 };
+// MIN / MAX over a string argument of up to kKeyWidth bytes: a whole line is one order key.  Words 0-5 hold the
+// string's bytes big-endian and zero-padded, each mapped to the signed order (^ 2^63); word 6 holds its length
+// (signed); word 7 is spare.  For MIN every used word is complemented, so that "greatest tuple" is the smallest
+// string.  The identity of every word is INT64_MIN: the empty string's byte words equal it under MAX, and its length
+// word 0 > INT64_MIN still beats "no row"; zero padding makes "ab" and "ab\0" equal in the byte words and the
+// length word puts the prefix first.  ``strdesc`` [stride] names per word of such a line its place in the tuple + 1
+// (0: the spare word, or a line not in use).  agg_multi sees the line as MA_MAX with unused slots (every pane starts
+// it at INT64_MIN); dxa_win_strkey fills it after the multi-aggregate.
+enum : int32_t { MA_STRKEY = 8 };
 
 // same layout as hash_groupby.hip's KeyCols (built by dxa/ops/hashing.py key_cols)
 struct KeyCol {
@@ -149,7 +162,12 @@ __device__ __forceinline__ uint64_t key_word(const KeyCol& k, int64_t i) {
 // for ``last``.  R, P and V of one pick choose the same slot, so a block slot holds a consistent (K, R, P, V) again
 // (its R only says "has a row": nothing decodes a combined rank).  No such slot gives the line's identity.  Without
 // kPick the branch is compiled out.
-template <bool kBlock, bool kM2, bool kMom, bool kKey, bool kPick>
+// ``kStr``: the layout has MA_STRKEY lines and ``strdesc`` [stride] names each of their words' place in the line's
+// 7-word tuple.  Such a word is taken from the slot whose tuple is lexicographically greatest (the first such slot;
+// equal tuples hold equal words), so the line stays one string's key; slots that are all the identity give the
+// identity.  A maximum over a total order: associative, so block slots and scratch slots combine like panes.
+// Without kStr the branch is compiled out.
+template <bool kBlock, bool kM2, bool kMom, bool kKey, bool kPick, bool kStr>
 __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long long* __restrict__ ring,
                                                           int64_t slot_words, const int32_t* __restrict__ slots,
                                                           int32_t nslots_in, int32_t stride,
@@ -159,7 +177,8 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
                                                           const int32_t* __restrict__ m2desc,
                                                           const int32_t* __restrict__ momdesc,
                                                           const int32_t* __restrict__ lodesc,
-                                                          const int32_t* __restrict__ pickdesc) {
+                                                          const int32_t* __restrict__ pickdesc,
+                                                          const int32_t* __restrict__ strdesc) {
   int32_t ng = scal[0];
   if (ng > gcap) ng = gcap;
   const int64_t held = (int64_t)ng * stride;
@@ -268,6 +287,31 @@ __global__ __launch_bounds__(256) void win_combine_kernel(const unsigned long lo
         if (!last) break;
       }
       out[idx] = acc;
+    } else if (kStr && op == MA_STRKEY) {
+      const int32_t dsc = strdesc[w];
+      const int ns_in = dsc ? nslots : 0;
+      const int64_t t_at = idx - (w & 7);
+      const long long none = (long long)0x8000000000000000ull;
+      long long top[7] = {none, none, none, none, none, none, none};
+      for (int s = 0; s < ns_in; ++s) {
+        const unsigned long long* t = ring + (int64_t)slots[s] * slot_words + t_at;
+        bool greater = false;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) {
+          const long long v = (long long)t[q];
+          if (v != top[q]) {
+            greater = v > top[q];
+            break;
+          }
+        }
+        if (!greater) continue;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) top[q] = (long long)t[q];
+      }
+      long long acc = none;
+#pragma unroll
+      for (int q = 0; q < 7; ++q) acc = dsc == q + 1 ? top[q] : acc;
+      out[idx] = (unsigned long long)acc;
     } else {
       long long acc = (long long)0x8000000000000000ull;
       for (int s = 0; s < nslots; ++s) {
@@ -336,7 +380,7 @@ __global__ __launch_bounds__(256) void win_compact_kernel(const uint8_t* __restr
 // host's group count is a batch stale — so both halves are always correct.  One launch covers all of a statement's
 // variance arguments, one after the other through the same LDS array.
 constexpr int kMaxM2Args = 8;
-constexpr int kM2LdsGroups = 1024;
+constexpr int kM2LdsGroups = dxa::kLdsGroupIds;      // (str_minmax.hip's arg-extreme kernel uses the same bound)
 struct M2Arg {
   const double* x;
   const uint8_t* valid;
@@ -644,6 +688,63 @@ __global__ __launch_bounds__(256) void win_pick_gather_kernel(const PickArgs m) 
   }
 }
 
+// 2f. the same second pass for MIN / MAX over strings.  Per job str_minmax.hip's arg-extreme kernel (dxa_str_argext,
+// over the pane's rows with the pane's ids and WHERE mask; the dump row's id gcap is outside its [0, gcap)) leaves in
+// ``best`` [job][gcap] the pane's winning row per group, then win_strkey_gather_kernel — threads stride over the
+// groups in use, as win_pick_gather_kernel's do — checks each index against [0, n) before any load and writes the
+// winner's packed words into the job's MA_STRKEY line.  A winner longer than kKeyWidth bytes has no key: status bit 8
+// is set (never cleared; the host sends the statement to the paned path) and the line keeps the identity.  A later
+// job that could reuse the line for a row pick's string payload only needs another source of the row index.
+constexpr int kMaxStrJobs = 8;
+struct StrJob {
+  const uint8_t* arena;
+  const int64_t* starts;
+  const int32_t* lens;
+  const uint8_t* valid;
+  int32_t line;            // the first word of the job's line in the slot row (a multiple of 8)
+  int32_t min;             // 1: MIN (every used word complemented)
+};
+struct StrKeyArgs {
+  StrJob a[kMaxStrJobs];
+  const int32_t* gid;
+  const uint8_t* keep;     // the pane's WHERE mask or null
+  unsigned long long* row; // the ring slot: [gcap + 1][stride]
+  int32_t* scal;           // the dictionary's status: scal[0] = groups in use, scal[1] |= 8: a winner too long
+  int64_t* best;           // [njobs][gcap] scratch
+  int64_t n;
+  int32_t gcap;
+  int32_t stride;
+  int32_t njobs;
+  int32_t pad;
+};
+
+__global__ __launch_bounds__(256) void win_strkey_gather_kernel(const StrKeyArgs m) {
+  int32_t ng = m.scal[0];
+  if (ng > m.gcap) ng = m.gcap;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long* r = m.row + g * m.stride;
+    for (int k = 0; k < m.njobs; ++k) {
+      const StrJob a = m.a[k];
+      const long long i = m.best[(int64_t)k * m.gcap + g];
+      if (i < 0 || i >= m.n) continue;
+      const int32_t l = a.lens[i];
+      if (l < 0 || l > kKeyWidth) {
+        atomicOr(&m.scal[1], 8);
+        continue;
+      }
+      const uint8_t* p = a.arena + a.starts[i];
+#pragma unroll
+      for (int q = 0; q < kKeyWidth / 8; ++q) {
+        const int32_t left = l - 8 * q;
+        const uint64_t w = left <= 0 ? 0ull : __builtin_bswap64(dxa::load_le(p + 8 * q, left < 8 ? left : 8));
+        const long long key = (long long)(w ^ 0x8000000000000000ull);
+        r[a.line + q] = (unsigned long long)(a.min ? ~key : key);
+      }
+      r[a.line + kKeyWidth / 8] = (unsigned long long)(a.min ? ~(long long)l : (long long)l);
+    }
+  }
+}
+
 __device__ __forceinline__ uint64_t row_hash(const KeyCols& a, int64_t i) {
   uint64_t h = 0;
   for (int j = 0; j < a.ncols; ++j) {
@@ -784,6 +885,11 @@ enum : int { F_COVAR_POP = 32, F_COVAR_SAMP = 64, F_CORR = 96, F_SKEW = 128, F_K
 //   F_DEC_AVG  the same words, cnt = n: total · 10^4 / n rounded HALF_UP (away from zero at a tie), exactly
 //   F_DEC_MM   pos = the high key word (F_NOT: MIN, complemented), op2 = the low key word: the key mapping undone
 enum : int { F_DEC_MM = 7, F_DEC_SUM = 192, F_DEC_AVG = 224, F_HI = 16 };
+// A byte word of a string MIN / MAX key (MA_STRKEY): MIN's complement (F_NOT), then the order mapping, undone — the
+// eight bytes big-endian again.  Its length word is finished as F_I64 (| F_NOT).  The kinds 0-7 and every multiple of
+// 32 up to 224 are taken, so this one is the exception to the rule above: bits 5-7 AND a low bit set, with no further
+// operand (emit_ok's range tests on the multi-operand kinds do not reach it, and F_KIND_MASK keeps it whole).
+enum : int { F_STRW = 33 };
 struct EmitArgs {
   const long long* acc;
   int32_t stride;
@@ -923,6 +1029,7 @@ __global__ __launch_bounds__(256) void win_emit_kernel(const EmitArgs e, DictCol
           o = (k & F_HI) ? v : (l ^ (long long)0x8000000000000000ull);
           break;
         }
+        case F_STRW: o = v ^ (long long)0x8000000000000000ull; break;
         default: o = v; break;
       }
       e.dst[(int64_t)r * e.gcap + p] = o;
@@ -968,7 +1075,8 @@ __global__ __launch_bounds__(256) void win_remap_slot_kernel(const unsigned long
     const int64_t p = idx / stride;
     const int w = (int)(idx - p * stride);
     const int op = line_op[w >> 3];
-    const bool lowest = op == MA_MAX_I64 || op == MA_LOKEY || op == MA_PICK_RANK;      // (MA_PICK_VAL words start at 0)
+    // (MA_PICK_VAL words start at 0)
+    const bool lowest = op == MA_MAX_I64 || op == MA_LOKEY || op == MA_PICK_RANK || op == MA_STRKEY;
     unsigned long long v = lowest ? 0x8000000000000000ull : 0ull;
     if (p < live) v = src[out_idx[p] * stride + w];
     dst[idx] = v;
@@ -1232,14 +1340,25 @@ static bool pickdesc_ok(const int32_t* host_desc, int32_t stride) {
   return true;
 }
 
+// (per word its place in the line's tuple + 1, so word w of a line holds (w & 7) + 1; 0: spare or unused)
+static bool strdesc_ok(const int32_t* host_desc, int32_t stride) {
+  for (int w = 0; w < stride; ++w) {
+    const int32_t d = host_desc[w];
+    if (d && (d != (w & 7) + 1 || d > 7)) return false;
+  }
+  return true;
+}
+
 static bool descs_ok(const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
                      const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
-                     const int32_t* pickdesc, const int32_t* pickdesc_host, int32_t stride) {
+                     const int32_t* pickdesc, const int32_t* pickdesc_host, const int32_t* strdesc,
+                     const int32_t* strdesc_host, int32_t stride) {
   if (!m2desc != !m2desc_host || !momdesc != !momdesc_host || (momdesc && !m2desc) || !lodesc != !lodesc_host ||
-      !pickdesc != !pickdesc_host)
+      !pickdesc != !pickdesc_host || !strdesc != !strdesc_host)
     return false;
   return (!m2desc || m2desc_ok(m2desc_host, stride)) && (!momdesc || momdesc_ok(momdesc_host, stride)) &&
-         (!lodesc || lodesc_ok(lodesc_host, stride)) && (!pickdesc || pickdesc_ok(pickdesc_host, stride));
+         (!lodesc || lodesc_ok(lodesc_host, stride)) && (!pickdesc || pickdesc_ok(pickdesc_host, stride)) &&
+         (!strdesc || strdesc_ok(strdesc_host, stride));
 }
 
 static bool folds_ok(const PairFolds* pf, int32_t stride) {
@@ -1267,29 +1386,37 @@ static bool emit_ok(const EmitArgs& ea, int32_t stride) {
 
 // The combine of ``slots`` into ``out`` with the instantiation the (checked) descriptors call for: the per-batch form
 // over the groups in use, or (kBlock) the block form that writes all gcap + 1 rows.
+template <bool kBlock, bool kKey, bool kPick, bool kStr>
+static void launch_combine_as(const unsigned long long* ring, int32_t gcap, int32_t stride, const int32_t* slots,
+                              int32_t nslots, const int32_t* line_op, const int32_t* scal, unsigned long long* out,
+                              const int32_t* m2desc, const int32_t* momdesc, const int32_t* lodesc,
+                              const int32_t* pickdesc, const int32_t* strdesc, hipStream_t s) {
+  const int32_t rows = kBlock ? gcap + 1 : gcap;
+  auto kernel = momdesc  ? win_combine_kernel<kBlock, true, true, kKey, kPick, kStr>
+                : m2desc ? win_combine_kernel<kBlock, true, false, kKey, kPick, kStr>
+                         : win_combine_kernel<kBlock, false, false, kKey, kPick, kStr>;
+  hipLaunchKernelGGL(kernel, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s, ring,
+                     (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap, kBlock ? rows : 0, out,
+                     m2desc, momdesc, lodesc, pickdesc, strdesc);
+}
+
+// one instantiation per combination of descriptors present: a layout without a family runs the combine without
+// that family's branch
 template <bool kBlock>
 static void launch_combine(const unsigned long long* ring, int32_t gcap, int32_t stride, const int32_t* slots,
                            int32_t nslots, const int32_t* line_op, const int32_t* scal, unsigned long long* out,
                            const int32_t* m2desc, const int32_t* momdesc, const int32_t* lodesc,
-                           const int32_t* pickdesc, hipStream_t s) {
-  const int32_t rows = kBlock ? gcap + 1 : gcap;
-  auto plain = momdesc  ? win_combine_kernel<kBlock, true, true, false, false>
-               : m2desc ? win_combine_kernel<kBlock, true, false, false, false>
-                        : win_combine_kernel<kBlock, false, false, false, false>;
-  auto keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true, false>
-               : m2desc ? win_combine_kernel<kBlock, true, false, true, false>
-                        : win_combine_kernel<kBlock, false, false, true, false>;
-  // with row picks (``pickdesc``): the same choices, with the pick branch
-  auto pick_plain = momdesc  ? win_combine_kernel<kBlock, true, true, false, true>
-                    : m2desc ? win_combine_kernel<kBlock, true, false, false, true>
-                             : win_combine_kernel<kBlock, false, false, false, true>;
-  auto pick_keyed = momdesc  ? win_combine_kernel<kBlock, true, true, true, true>
-                    : m2desc ? win_combine_kernel<kBlock, true, false, true, true>
-                             : win_combine_kernel<kBlock, false, false, true, true>;
-  auto kernel = pickdesc ? (lodesc ? pick_keyed : pick_plain) : (lodesc ? keyed : plain);
-  hipLaunchKernelGGL(kernel, dim3(dxa_blocks((int64_t)rows * stride, 256, 256 * 64)), dim3(256), 0, s, ring,
-                     (int64_t)(gcap + 1) * stride, slots, nslots, stride, line_op, scal, gcap, kBlock ? rows : 0, out,
-                     m2desc, momdesc, lodesc, pickdesc);
+                           const int32_t* pickdesc, const int32_t* strdesc, hipStream_t s) {
+  auto plain = launch_combine_as<kBlock, false, false, false>, keyed = launch_combine_as<kBlock, true, false, false>,
+       pick_plain = launch_combine_as<kBlock, false, true, false>,
+       pick_keyed = launch_combine_as<kBlock, true, true, false>,
+       str_plain = launch_combine_as<kBlock, false, false, true>,
+       str_keyed = launch_combine_as<kBlock, true, false, true>,
+       str_pick_plain = launch_combine_as<kBlock, false, true, true>,
+       str_pick_keyed = launch_combine_as<kBlock, true, true, true>;
+  auto launch = strdesc ? (pickdesc ? (lodesc ? str_pick_keyed : str_pick_plain) : (lodesc ? str_keyed : str_plain))
+                        : (pickdesc ? (lodesc ? pick_keyed : pick_plain) : (lodesc ? keyed : plain));
+  launch(ring, gcap, stride, slots, nslots, line_op, scal, out, m2desc, momdesc, lodesc, pickdesc, strdesc, s);
 }
 
 // a block of ring slots pre-combined into another ring slot (every row is written, so groups the dictionary gains
@@ -1298,12 +1425,14 @@ DXA_API int dxa_win_combine_block(void* ring, int32_t gcap, int32_t stride, cons
                                   const int32_t* line_op, int32_t dst, const int32_t* scal, const int32_t* m2desc,
                                   const int32_t* m2desc_host, const int32_t* momdesc, const int32_t* momdesc_host,
                                   const int32_t* lodesc, const int32_t* lodesc_host, const int32_t* pickdesc,
-                                  const int32_t* pickdesc_host, void* st) {
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, stride))
+                                  const int32_t* pickdesc_host, const int32_t* strdesc, const int32_t* strdesc_host,
+                                  void* st) {
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, strdesc,
+                strdesc_host, stride))
     return (int)hipErrorInvalidValue;
   unsigned long long* r = (unsigned long long*)ring;
   launch_combine<true>(r, gcap, stride, slots, nslots, line_op, scal, r + (int64_t)dst * (gcap + 1) * stride, m2desc,
-                       momdesc, lodesc, pickdesc, (hipStream_t)st);
+                       momdesc, lodesc, pickdesc, strdesc, (hipStream_t)st);
   return (int)hipGetLastError();
 }
 
@@ -1316,16 +1445,18 @@ DXA_API int dxa_win_answer(const void* ring, int32_t gcap, int32_t stride, const
                            int64_t* out_idx, const void* emit, const void* dictcols, const void* folds,
                            const int32_t* m2desc, const int32_t* m2desc_host, const int32_t* momdesc,
                            const int32_t* momdesc_host, const int32_t* lodesc, const int32_t* lodesc_host,
-                           const int32_t* pickdesc, const int32_t* pickdesc_host, void* st) {
+                           const int32_t* pickdesc, const int32_t* pickdesc_host, const int32_t* strdesc,
+                           const int32_t* strdesc_host, void* st) {
   hipStream_t s = (hipStream_t)st;
   const EmitArgs* ea = (const EmitArgs*)emit;
   const PairFolds* pf = (const PairFolds*)folds;
-  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, stride) ||
+  if (!descs_ok(m2desc, m2desc_host, momdesc, momdesc_host, lodesc, lodesc_host, pickdesc, pickdesc_host, strdesc,
+                strdesc_host, stride) ||
       !folds_ok(pf, stride) || (ea && (!dictcols || !emit_ok(*ea, stride))))
     return (int)hipErrorInvalidValue;
   hipMemsetAsync(scal + 2, 0, 4, s);
   launch_combine<false>((const unsigned long long*)ring, gcap, stride, slots, nslots, line_op, scal,
-                        (unsigned long long*)acc, m2desc, momdesc, lodesc, pickdesc, s);
+                        (unsigned long long*)acc, m2desc, momdesc, lodesc, pickdesc, strdesc, s);
   for (int k = 0; pf && k < pf->n; ++k) {
     auto fold = pf->p[k].isum >= 0 || pf->p[k].fsum >= 0 ? win_distinct_fold_kernel<true>
                                                          : win_distinct_fold_kernel<false>;
@@ -1351,7 +1482,8 @@ DXA_API int dxa_win_live(const void* ring, int32_t gcap, int32_t stride, const i
                          const int32_t* line_op, int32_t count_word, int32_t* scal, void* acc, uint8_t* keep,
                          int64_t* out_idx, void* st) {
   return dxa_win_answer(ring, gcap, stride, slots, nslots, line_op, count_word, scal, acc, keep, out_idx, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, st);
 }
 
 // The dictionary's key columns into fresh ones (``dst`` is zero-filled; earlier batches' output strings are views of
@@ -1455,7 +1587,8 @@ DXA_API int dxa_win_pair_or_block(uint8_t* pres, int64_t pitch, const int32_t* s
 
 DXA_API int dxa_win_m2_size() { return (int)sizeof(M2Args); }
 
-// ids below this are summed in LDS by win_m2_kernel, the others add straight to global memory
+// ids below this go through LDS in win_m2_kernel and the other second passes (dxa::kLdsGroupIds: str_minmax.hip's
+// bound too), the others straight to global memory
 DXA_API int dxa_win_m2_lds_groups() { return kM2LdsGroups; }
 
 // a pane's M2 words, on the same stream right after dxa_aggregate_multi filled the slot (win_m2_kernel)
@@ -1509,6 +1642,36 @@ DXA_API int dxa_win_dec(const void* args, void* st) {
   }
   if (m.n <= 0 || m.nargs == 0) return 0;
   hipLaunchKernelGGL(win_dec_kernel, dim3(dxa_blocks((m.n + 7) / 8, 256, 512)), dim3(256), 0, (hipStream_t)st, m);
+  return (int)hipGetLastError();
+}
+
+// ---- MIN / MAX over strings: the pane's string pass ---------------------------------------------------------------
+
+extern "C" int dxa_str_argext(const int32_t* gid, int64_t n, int32_t ngroups, const uint8_t* arena,
+                              const int64_t* starts, const int32_t* lens, const uint8_t* valid, const uint8_t* keep,
+                              int32_t dir, int64_t* best, void* st);       // str_minmax.hip
+
+DXA_API int dxa_win_strkey_size() { return (int)sizeof(StrKeyArgs); }
+
+// a pane's string order keys, on the same stream after dxa_aggregate_multi initialised the slot: per job the winning
+// row per group (str_minmax.hip), then every job's packed words in one gather launch (win_strkey_gather_kernel)
+DXA_API int dxa_win_strkey(const void* args, void* st) {
+  const StrKeyArgs& m = *(const StrKeyArgs*)args;
+  if (m.njobs < 1 || m.njobs > kMaxStrJobs || m.gcap < 0 || m.stride <= 0 || !m.gid || !m.row || !m.scal || !m.best)
+    return (int)hipErrorInvalidValue;
+  for (int k = 0; k < m.njobs; ++k) {
+    const StrJob& a = m.a[k];
+    if (!a.starts || !a.lens || a.line < 0 || (a.line & 7) || a.line + 8 > m.stride || (a.min != 0 && a.min != 1))
+      return (int)hipErrorInvalidValue;
+  }
+  if (m.n <= 0) return 0;
+  for (int k = 0; k < m.njobs; ++k) {
+    const StrJob& a = m.a[k];
+    const int rc = dxa_str_argext(m.gid, m.n, m.gcap, a.arena, a.starts, a.lens, a.valid, m.keep, a.min ? 0 : 1,
+                                  m.best + (int64_t)k * m.gcap, st);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(win_strkey_gather_kernel, dim3(dxa_blocks(m.gcap, 256, 1024)), dim3(256), 0, (hipStream_t)st, m);
   return (int)hipGetLastError();
 }
 

@@ -247,6 +247,8 @@ def aggregate(groups: Groups, col, func: str, n: int):
         return col.take(idx)
     if isinstance(col, StrColumn) or not isinstance(col, PrimColumn):
         if func in ("min", "max"):
+            if type(col) is StrColumn and _on_gpu(device):
+                return _str_minmax(groups, col, func, n, device)
             return _host_minmax(groups, col, func, device)
         raise TypeError(f"{func} over {col.dtype} is not supported")
     dt = col.dtype
@@ -298,8 +300,31 @@ def _central_m2(groups, x, valid, c, n, device):
     return _agg_raw(groups, d * d, valid, "sum", n, device)
 
 
+def str_argext(gid: torch.Tensor, n: int, ngroups: int, col, func: str, keep: Optional[torch.Tensor] = None):
+    """Per group the index of a row holding its MIN / MAX string (str_minmax.hip: unsigned byte order, a prefix before
+    the longer string, the smallest index among equals), -1 for a group without a non-NULL row.  ``gid``: int32 ids,
+    those outside [0, ngroups) are skipped, as are the rows a ``keep`` mask (uint8) drops."""
+    best = torch.empty(ngroups, dtype=torch.int64, device=gid.device)
+    valid = N.u8(col.valid)
+    if valid is not None:
+        valid = valid.contiguous()
+    N.call("dxa_str_argext", N.ptr(gid), n, ngroups, N.ptr(col.arena), N.ptr(col.starts.contiguous()),
+           N.ptr(col.lens.contiguous()), N.ptr(valid), N.ptr(keep), 1 if func == "max" else 0, N.ptr(best),
+           N.stream_handle(gid.device))
+    return best
+
+
+def _str_minmax(groups, col, func, n, device):
+    """MIN / MAX over a string column on the device: the winning rows' strings as views of the column's arena, NULL
+    for a group without a non-NULL row.  No host synchronisation."""
+    gid = groups.gid if groups.gid.dtype == torch.int32 else groups.gid.to(torch.int32)
+    idx = str_argext(gid.contiguous(), n, groups.ngroups, col, func)
+    miss = idx < 0
+    return col.take(torch.where(miss, torch.zeros_like(idx), idx)).with_valid(~miss)
+
+
 def _host_minmax(groups, col, func, device):
-    """MIN/MAX over strings (and other non-numeric types): host-assisted, rarely on a hot path."""
+    """MIN/MAX over non-numeric types other than device strings: host-assisted, rarely on a hot path."""
     from ..engine.column import column_from_pylist
     vals = col.to_pylist()
     gid = groups.gid.cpu().tolist()
@@ -338,6 +363,11 @@ _DEC_SUM, _DEC_KEY_MAX, _DEC_KEY_MIN = 0, 1, 2           # win_dec_kernel's job 
 # last << 16 | 1 << 17
 _MA_PICK_RANK, _MA_PICK_VAL = 6, 7
 _PICK_LAST, _PICK_USED = 1 << 16, 1 << 17
+# and for MIN / MAX over strings of up to 48 bytes: the combine op of a line that is one order key — six big-endian
+# byte words and a length word, each mapped to the signed order and complemented for MIN, and a spare word — and the
+# finishing kind that undoes a byte word's mapping (the length word is an _F_I64 word)
+_MA_STRKEY = 8
+_F_STRW = 33
 _FUSABLE = ("count_star", "count", "sum", "min", "max", "avg", "mean")
 # below this many groups the per-aggregate LDS-privatised kernels win (hot lines would serialise at the memory side)
 FUSED_MIN_GROUPS = 4096

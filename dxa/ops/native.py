@@ -73,6 +73,7 @@ _SIGS = {
     "dxa_str_cmp_lit": [c_p, c_p, c_p, c_i64, c_p, c_i32, c_i32, c_p, c_p],
     "dxa_str_eq_col": [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p],
     "dxa_str_cmp_col": [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_p],
+    "dxa_str_argext": [c_p, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_p],
     "dxa_str_gather": [c_p, c_p, c_p, c_i64, c_p, c_p, c_p],
     "dxa_str_gather_parts": [c_p, c_i32, c_p],
     "dxa_str_split_count": [c_p, c_p, c_p, c_i64, c_p, c_i32, c_p, c_p],
