@@ -1772,27 +1772,41 @@ def _moments(name, args, groups: G.Groups):
     cnt = gsum(torch.ones_like(vals[0]))
     safe = cnt.clamp(min=1)
     d = [v - (gsum(v) / safe)[gid] for v in vals]
-    has = cnt > 0
-    nan = torch.full_like(cnt, float("nan"))
     if name in ("corr", "covar_pop", "covar_samp"):
         if len(d) != 2:
             raise QueryError(f"{name} takes two arguments")
         cxy = gsum(d[0] * d[1])
-        if name == "covar_pop":
-            return PrimColumn("double", cxy / safe, has)
-        if name == "covar_samp":
-            return PrimColumn("double", torch.where(cnt > 1, cxy / (cnt - 1).clamp(min=1), nan), has)
-        den = torch.sqrt(gsum(d[0] * d[0]) * gsum(d[1] * d[1]))
-        return PrimColumn("double", torch.where(den > 0, cxy / torch.where(den > 0, den, torch.ones_like(den)), nan),
-                          has)
-    m2, m = gsum(d[0] * d[0]), cnt
+        if name == "corr":
+            return finish_comoments(name, cnt, cxy, gsum(d[0] * d[0]), gsum(d[1] * d[1]))
+        return finish_comoments(name, cnt, cxy)
+    m2 = gsum(d[0] * d[0])
     if name == "skewness":
-        m3 = gsum(d[0] ** 3)
-        r = torch.sqrt(m) * m3 / torch.where(m2 > 0, m2, torch.ones_like(m2)) ** 1.5
+        return finish_moments(name, cnt, m2, m3=gsum(d[0] ** 3))
+    return finish_moments(name, cnt, m2, m4=gsum(d[0] ** 4))
+
+
+def finish_comoments(name, cnt, cxy, m2x=None, m2y=None):
+    """covar_pop / covar_samp / corr from the count (as doubles) and the central sums Cxy = Σ dx·dy, M2x, M2y (the
+    last two for corr only) — per group above, per window frame in engine/windowfn.py."""
+    has = cnt > 0
+    nan = torch.full_like(cnt, float("nan"))
+    if name == "covar_pop":
+        return PrimColumn("double", cxy / cnt.clamp(min=1), has)
+    if name == "covar_samp":
+        return PrimColumn("double", torch.where(cnt > 1, cxy / (cnt - 1).clamp(min=1), nan), has)
+    den = torch.sqrt(m2x * m2y)
+    return PrimColumn("double", torch.where(den > 0, cxy / torch.where(den > 0, den, torch.ones_like(den)), nan),
+                      has)
+
+
+def finish_moments(name, cnt, m2, m3=None, m4=None):
+    """skewness (from M3) / excess kurtosis (from M4) of ``cnt`` values with central sums M2, M3, M4; NaN unless
+    M2 > 0."""
+    if name == "skewness":
+        r = torch.sqrt(cnt) * m3 / torch.where(m2 > 0, m2, torch.ones_like(m2)) ** 1.5
     else:
-        m4 = gsum(d[0] ** 4)
-        r = m * m4 / torch.where(m2 > 0, m2 * m2, torch.ones_like(m2)) - 3.0
-    return PrimColumn("double", torch.where(m2 > 0, r, nan), has)
+        r = cnt * m4 / torch.where(m2 > 0, m2 * m2, torch.ones_like(m2)) - 3.0
+    return PrimColumn("double", torch.where(m2 > 0, r, torch.full_like(cnt, float("nan"))), cnt > 0)
 
 
 def _arg_extreme(args, groups: G.Groups, n, is_max: bool):

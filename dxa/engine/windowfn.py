@@ -11,7 +11,16 @@ every statement to ``spark.sql``); here each window call is evaluated column-at-
    ``nth_value`` are gathers; aggregates over a frame ``[a, b]`` use prefix sums for counts and integer / decimal
    sums (exact: int64 and 32-bit decimal limbs), power-of-two block sums for double sums (no prefix differences,
    which cancel catastrophically) and a sparse table for min/max (O(n log n) build, O(1) query);
+   the variance and moment families (stddev / variance and their _pop / _samp forms, skewness, kurtosis, covar_pop,
+   covar_samp, corr) take their frame's state — (n, mean, M2), (n, mean, M2, M3, M4) or (n, mean_x, mean_y, Cxy,
+   M2x, M2y) — from the HIP kernels of ``ops/csrc/window_frames.hip``: one two-pass launch when the longest frame
+   is at most ``FRAME_DIRECT_MAX`` rows, else one launch per power-of-two level with pairwise (Chan) merges; on a
+   CPU device the same level algorithm runs as tensor operations (``_frame_state_tensor``).  The state is finished
+   by the rules GROUP BY uses (``groupby.finish_variance``, ``query.finish_moments`` / ``finish_comoments``);
 4. the result is scattered back to input row order.
+
+Known caveat, shared with GROUP BY: ``M2 > 0`` is tested on a rounded M2, so corr / skewness / kurtosis of a constant
+frame whose values do not sum exactly can be a huge number where Spark gives NaN.
 
 Distributed scopes are re-partitioned by the PARTITION BY keys (RCCL all-to-all) before evaluation, or gathered when
 there is no PARTITION BY (see ``query._exec_select``).
@@ -23,16 +32,34 @@ from typing import Callable, List
 import torch
 
 from ..ops import groupby as G
+from ..ops import native as N
 from ..sql import ast as A
 from .column import Column, ConstColumn, PrimColumn, materialize
+
+N.register_sigs({
+    "dxa_frame_moments_direct": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p],
+    "dxa_frame_moments_levels": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_i64, N.c_p, N.c_p, N.c_p],
+})
 
 RANKING = {"row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile"}
 OFFSET = {"lag", "lead"}
 VALUE = {"first_value", "last_value", "first", "last", "nth_value"}
 FRAMED_AGGS = {"sum", "count", "avg", "mean", "min", "max"}
-WINDOW_FUNCS = RANKING | OFFSET | VALUE | FRAMED_AGGS
+# state kinds of window_frames.hip: VAR (n, mean, M2), MOM (n, mean, M2, M3, M4), CO (n, mean_x, mean_y, Cxy, M2x, M2y)
+KIND_VAR, KIND_MOM, KIND_CO = 0, 1, 2
+STATE_WORDS = {KIND_VAR: 3, KIND_MOM: 5, KIND_CO: 6}
+FRAME_MOMENTS = {"stddev": KIND_VAR, "std": KIND_VAR, "stddev_samp": KIND_VAR, "stddev_pop": KIND_VAR,
+                 "variance": KIND_VAR, "var_samp": KIND_VAR, "var_pop": KIND_VAR, "skewness": KIND_MOM,
+                 "kurtosis": KIND_MOM, "covar_pop": KIND_CO, "covar_samp": KIND_CO, "corr": KIND_CO}
+WINDOW_FUNCS = RANKING | OFFSET | VALUE | FRAMED_AGGS | set(FRAME_MOMENTS)
+
+# The longest frame (rows) the one-launch two-pass kernel takes; longer frames go level by level.  The longest
+# measured frame at which the direct entry was no slower than the levels entry for every state kind
+# (profiles/window_frames/README.md).
+FRAME_DIRECT_MAX = 48
 
 _INT_TYPES = ("byte", "short", "int", "integer", "long", "bigint", "tinyint", "smallint")
+_FLOAT_TYPES = ("float", "double")
 
 
 class WindowError(Exception):
@@ -269,6 +296,11 @@ def _compute(name, wc, ev, perm, idx, pstart, pend, peer_new, peer_start, peer_e
             out = _select_by_conditions([PrimColumn("boolean", ok)], [out], dflt, n, dev)
         return out
 
+    if name in FRAME_MOMENTS:
+        cols = _moment_args(name, wc, ev, perm)
+        a, b = _frame(wc, idx, pstart, pend, peer_start, peer_end, rkey)
+        return _frame_moment_agg(name, cols, a, b, n, dev)
+
     if wc.func.star or (name == "count" and not args):
         x = None
     else:
@@ -339,6 +371,132 @@ def _compute(name, wc, ev, perm, idx, pstart, pend, peer_new, peer_start, peer_e
         fill = info.min if is_max else info.max
     masked = torch.where(valid, data, torch.full_like(data, fill))
     return PrimColumn(x.dtype, _minmax_frame(masked, a, b, is_max), has)
+
+
+def _moment_args(name, wc, ev, perm):
+    """The argument column(s) of a variance / moment window aggregate as double columns in sorted order."""
+    from .decimal import is_decimal, to_double
+    args = wc.func.args
+    if wc.func.star or len(args) != (2 if FRAME_MOMENTS[name] == KIND_CO else 1):
+        raise WindowError(f"wrong number of arguments to {name}")
+    cols = []
+    for e in args:
+        x = materialize(ev(e))
+        if isinstance(x, ConstColumn):
+            x = x.materialize()
+        if not isinstance(x, PrimColumn) or not (is_decimal(x.dtype) or x.dtype in _INT_TYPES + _FLOAT_TYPES):
+            raise WindowError(f"{name} OVER needs a numeric argument")
+        if is_decimal(x.dtype):
+            x = to_double(x)                              # as Spark casts it
+        cols.append(x.take(perm))
+    return cols
+
+
+def _frame_moment_agg(name, cols, a, b, n, dev):
+    """stddev / variance / skewness / kurtosis / covar / corr of ``cols`` over the frames ``[a, b]``: the frame's
+    moment state from ``_frame_state``, then the finishing rules GROUP BY uses."""
+    from .column import and_valid
+    from .query import finish_comoments, finish_moments
+    kind = FRAME_MOMENTS[name]
+    x = cols[0].data.to(torch.float64).contiguous()
+    y = cols[1].data.to(torch.float64).contiguous() if kind == KIND_CO else None
+    valid = cols[0].valid
+    for c in cols[1:]:
+        valid = and_valid(valid, c.valid)                 # a pair counts where both arguments are non-NULL
+    length = torch.where(a <= b, b - a + 1, torch.zeros_like(a))
+    maxlen = int(length.max())                            # one host read: the path choice and the level count
+    if maxlen == 0:
+        st = torch.zeros((STATE_WORDS[kind], n), dtype=torch.float64, device=dev)
+    else:
+        st = _frame_state(kind, x, y, valid, a, b, maxlen)
+    if kind == KIND_VAR:
+        return G.finish_variance(name, st[0], st[2])
+    if kind == KIND_MOM:
+        return finish_moments(name, st[0], st[2], m3=st[3], m4=st[4])
+    return finish_comoments(name, st[0], st[3], st[4], st[5])
+
+
+def _frame_state(kind, x, y, valid, a, b, maxlen) -> torch.Tensor:
+    """The moment state of every frame ``x[a[i] .. b[i]]`` (``a > b``: empty) as f64 ``[words, n]``; ``maxlen`` ≥ 1
+    is the longest frame length.  Native on the GPU, tensor operations on the CPU."""
+    if N.use_native(x):
+        return _frame_state_native(kind, x, y, valid, a, b, maxlen)
+    return _frame_state_tensor(kind, x, y, valid, a, b, maxlen)
+
+
+def _frame_state_native(kind, x, y, valid, a, b, maxlen) -> torch.Tensor:
+    n = int(x.shape[0])
+    words = STATE_WORDS[kind]
+    out = torch.empty((words, n), dtype=torch.float64, device=x.device)
+    v = None if valid is None else N.u8(valid).contiguous()
+    a, b = a.contiguous(), b.contiguous()
+    st = N.stream_handle(x.device)
+    if maxlen <= FRAME_DIRECT_MAX:
+        N.call("dxa_frame_moments_direct", N.ptr(x), N.ptr(y), N.ptr(v), N.ptr(a), N.ptr(b), n, kind, N.ptr(out), st)
+    else:
+        scratch = torch.empty((2, words, n), dtype=torch.float64, device=x.device)     # two ping-pong levels
+        N.call("dxa_frame_moments_levels", N.ptr(x), N.ptr(y), N.ptr(v), N.ptr(a), N.ptr(b), n, kind, maxlen,
+               N.ptr(scratch), N.ptr(out), st)
+    return out
+
+
+def _merge_states(kind, A, B):
+    """Chan's pairwise merge of two moment states (lists of word tensors; A the left run, B the right); a side
+    with n = 0 returns the other unchanged."""
+    na, nb = A[0], B[0]
+    n = na + nb
+    sn = n.clamp(min=1)
+    if kind == KIND_CO:
+        dx, dy = B[1] - A[1], B[2] - A[2]
+        f = na * nb / sn
+        out = [n, A[1] + dx * nb / sn, A[2] + dy * nb / sn, A[3] + B[3] + dx * dy * f, A[4] + B[4] + dx * dx * f,
+               A[5] + B[5] + dy * dy * f]
+    else:
+        d = B[1] - A[1]
+        d2 = d * d
+        out = [n, A[1] + d * nb / sn, A[2] + B[2] + d2 * na * nb / sn]
+        if kind == KIND_MOM:
+            n2 = sn * sn
+            out.append(A[3] + B[3] + d2 * d * na * nb * (na - nb) / n2 + 3.0 * d * (na * B[2] - nb * A[2]) / sn)
+            out.append(A[4] + B[4] + d2 * d2 * na * nb * (na * na - na * nb + nb * nb) / (n2 * sn)
+                       + 6.0 * d2 * (na * na * B[2] + nb * nb * A[2]) / n2 + 4.0 * d * (na * B[3] - nb * A[3]) / sn)
+    only_a, only_b = nb == 0, na == 0
+    return [torch.where(only_a, wa, torch.where(only_b, wb, w)) for wa, wb, w in zip(A, B, out)]
+
+
+def _frame_state_tensor(kind, x, y, valid, a, b, maxlen) -> torch.Tensor:
+    """``_frame_state`` as vectorised tensor operations on any device — the level algorithm of
+    ``window_frames.hip``: level k holds the state of the 2^k-row run starting at every row (clipped at n), every
+    frame is cut into such runs by the bits of its length, lowest bit first, and states merge pairwise.  Nothing is
+    computed as Σx² − (Σx)²/n, and only values inside a frame enter its state."""
+    n = int(x.shape[0])
+    zero = torch.zeros_like(x)
+    ok = torch.ones_like(x, dtype=torch.bool) if valid is None else valid.to(torch.bool)
+
+    def own(v):
+        return torch.where(ok, v, zero)
+    zx = x - x                                             # 0, or NaN for a non-finite value
+    if kind == KIND_CO:
+        zy = y - y
+        level = [ok.to(torch.float64), own(x), own(y), own(zx * zy), own(zx), own(zy)]
+    else:
+        level = [ok.to(torch.float64), own(x)] + [own(zx)] * (STATE_WORDS[kind] - 2)
+    lo, hi = a.clamp(min=0), b.clamp(max=n - 1)            # frames are clipped to [0, n)
+    length = torch.where((a <= b) & (lo <= hi), hi - lo + 1, torch.zeros_like(a))
+    acc = [zero] * STATE_WORDS[kind]
+    k = 0
+    while (1 << k) <= maxlen:
+        step = 1 << k
+        take = ((length >> k) & 1).to(torch.bool)
+        pos = (lo + (length & (step - 1))).clamp(max=n - 1)
+        run = [w[pos] for w in level]
+        run[0] = torch.where(take, run[0], zero)           # bit k clear: merge the identity
+        acc = _merge_states(kind, acc, run)
+        if (step << 1) <= maxlen:
+            pad = min(step, n)
+            level = _merge_states(kind, level, [torch.cat([w[step:], zero[:pad]]) for w in level])
+        k += 1
+    return torch.stack(acc)
 
 
 def _float_frame_sum(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, nonempty: torch.Tensor) -> torch.Tensor:

@@ -279,14 +279,21 @@ def aggregate(groups: Groups, col, func: str, n: int):
     if func in ("stddev", "stddev_samp", "stddev_pop", "variance", "var_samp", "var_pop", "std"):
         c = (cnt if cnt is not None else _agg_raw(groups, None, None, "count", n, device)).to(torch.float64)
         m2 = _central_m2(groups, data.to(torch.float64), valid, c, n, device)
-        pop = func.endswith("_pop")
-        denom = c if pop else (c - 1)
-        var = m2 / denom.clamp(min=1)
-        out = var.sqrt() if func.startswith("std") else var
-        if not pop:            # Spark 2.4: the sample statistics of ONE row are NaN (null only for no rows)
-            out = torch.where(c == 1, torch.full_like(out, float("nan")), out)
-        return PrimColumn("double", out, c > 0)
+        return finish_variance(func, c, m2)
     raise ValueError(f"unsupported aggregate {func}")
+
+
+def finish_variance(func: str, c: torch.Tensor, m2: torch.Tensor) -> PrimColumn:
+    """stddev / variance (sample or ``_pop``) from the count ``c`` (as doubles) and M2 = Σ (x − mean)² — per group
+    here, per window frame in engine/windowfn.py."""
+    from ..engine.column import PrimColumn
+    pop = func.endswith("_pop")
+    denom = c if pop else (c - 1)
+    var = m2 / denom.clamp(min=1)
+    out = var.sqrt() if func.startswith("std") else var
+    if not pop:            # Spark 2.4: the sample statistics of ONE row are NaN (null only for no rows)
+        out = torch.where(c == 1, torch.full_like(out, float("nan")), out)
+    return PrimColumn("double", out, c > 0)
 
 
 def _central_m2(groups, x, valid, c, n, device):
