@@ -1862,6 +1862,26 @@ def _distinct_agg(name, arg, groups: G.Groups, n):
     return G.aggregate(owner, vals, "sum" if name == "sum" else "avg", int(first_rows.shape[0]))
 
 
+def percentile_ranks(q: float, cnt: torch.Tensor, exact: bool):
+    """The 0-based ranks, among ``cnt`` counted values in ascending order, that percentile ``q`` reads — per group
+    in ``_percentile``, per window frame in engine/windowfn.py.  Exact form: ``(lo, hi, fr)`` with pos = q·(cnt − 1),
+    lo = ⌊pos⌋, hi = min(lo + 1, cnt − 1), fr = pos − lo; approximate form: ``(k,)``, k = clamp(⌈q·cnt⌉ − 1, 0,
+    cnt − 1).  A count of 0 gives rank 0 (the caller's result is NULL there)."""
+    c1 = torch.clamp(cnt - 1, min=0)
+    if exact:
+        pos = q * c1.to(torch.float64)
+        lo = torch.floor(pos).to(torch.int64)
+        hi = torch.clamp(lo + 1, max=c1)
+        return lo, hi, pos - lo.to(torch.float64)
+    k = torch.clamp(torch.ceil(q * cnt.to(torch.float64)).to(torch.int64) - 1, min=0)
+    return (torch.minimum(k, c1),)
+
+
+def percentile_interpolate(vl: torch.Tensor, vh: torch.Tensor, fr: torch.Tensor) -> torch.Tensor:
+    """Linear interpolation between the values at ranks lo and hi of ``percentile_ranks``."""
+    return vl + fr * (vh - vl)
+
+
 def _percentile(groups: G.Groups, arg, p, exact: bool):
     """percentile / median (linear interpolation between the two nearest ranks) and percentile_approx (the
     smallest value whose rank reaches p·count — exact here) per group, from one device sort by (group, value).
@@ -1893,19 +1913,13 @@ def _percentile(groups: G.Groups, arg, p, exact: bool):
     cnt = torch.bincount(g, minlength=ng)
     start = torch.cumsum(cnt, 0) - cnt
     has = cnt > 0
-    c1 = torch.clamp(cnt - 1, min=0)
     if exact:
-        pos = q * c1.to(torch.float64)
-        lo = torch.floor(pos).to(torch.int64)
-        hi = torch.clamp(lo + 1, max=c1)
-        fr = pos - lo.to(torch.float64)
+        lo, hi, fr = percentile_ranks(q, cnt, True)
         vl = v[torch.clamp(start + lo, max=max(0, v.numel() - 1))] if v.numel() else torch.zeros(ng, dtype=torch.float64,
                                                                                                 device=dev)
         vh = v[torch.clamp(start + hi, max=max(0, v.numel() - 1))] if v.numel() else vl
-        r = vl + fr * (vh - vl)
-        return PrimColumn("double", r, has)
-    k = torch.clamp(torch.ceil(q * cnt.to(torch.float64)).to(torch.int64) - 1, min=0)
-    k = torch.minimum(k, c1)
+        return PrimColumn("double", percentile_interpolate(vl, vh, fr), has)
+    k = percentile_ranks(q, cnt, False)[0]
     if dec:
         at = idx[o][torch.clamp(start + k, max=max(0, v.numel() - 1))] if v.numel() else \
             torch.zeros(ng, dtype=torch.int64, device=dev)

@@ -17,6 +17,16 @@ every statement to ``spark.sql``); here each window call is evaluated column-at-
    is at most ``FRAME_DIRECT_MAX`` rows, else one launch per power-of-two level with pairwise (Chan) merges; on a
    CPU device the same level algorithm runs as tensor operations (``_frame_state_tensor``).  The state is finished
    by the rules GROUP BY uses (``groupby.finish_variance``, ``query.finish_moments`` / ``finish_comoments``);
+   the order statistics (percentile / median with linear interpolation, percentile_approx / approx_percentile — the
+   smallest counted value whose rank reaches p·count, exact here) have no mergeable state: the ranks they read come
+   from GROUP BY's own arithmetic (``query.percentile_ranks``) on the frame's count of non-NULL rows, and ONE
+   primitive (``_frame_select``) turns all ranks of a window call into row positions — "the k-th smallest counted
+   row of x[a[i] .. b[i]] in (order key, position) order" — from the HIP kernels of ``ops/csrc/window_select.hip``:
+   one launch that ranks every candidate of its frame when the longest frame is at most
+   ``FRAME_SELECT_DIRECT_MAX`` rows, else a wavelet matrix over the rows' global ranks (one stable radix sort, per
+   bit a prefix count and a stable scatter, then one launch that answers every row and rank); on a CPU device the
+   same wavelet build and query run as tensor operations (``_frame_select_tensor``).  The values at those
+   positions are gathered and interpolated (``query.percentile_interpolate``);
 4. the result is scattered back to input row order.
 
 Known caveat, shared with GROUP BY: ``M2 > 0`` is tested on a rounded M2, so corr / skewness / kurtosis of a constant
@@ -39,6 +49,9 @@ from .column import Column, ConstColumn, PrimColumn, materialize
 N.register_sigs({
     "dxa_frame_moments_direct": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p],
     "dxa_frame_moments_levels": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_i64, N.c_p, N.c_p, N.c_p],
+    "dxa_frame_select_direct": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_p, N.c_i32, N.c_p, N.c_p],
+    "dxa_frame_select_tree": [N.c_p, N.c_p, N.c_p, N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_i32, N.c_p, N.c_p],
+    "dxa_wavelet_level": [N.c_p, N.c_p, N.c_i64, N.c_i32, N.c_p, N.c_p, N.c_p],
 })
 
 RANKING = {"row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile"}
@@ -51,12 +64,18 @@ STATE_WORDS = {KIND_VAR: 3, KIND_MOM: 5, KIND_CO: 6}
 FRAME_MOMENTS = {"stddev": KIND_VAR, "std": KIND_VAR, "stddev_samp": KIND_VAR, "stddev_pop": KIND_VAR,
                  "variance": KIND_VAR, "var_samp": KIND_VAR, "var_pop": KIND_VAR, "skewness": KIND_MOM,
                  "kurtosis": KIND_MOM, "covar_pop": KIND_CO, "covar_samp": KIND_CO, "corr": KIND_CO}
-WINDOW_FUNCS = RANKING | OFFSET | VALUE | FRAMED_AGGS | set(FRAME_MOMENTS)
+# order statistics over a frame: True for the exact (interpolating) form, False for the approximate one
+FRAME_SELECT = {"percentile": True, "median": True, "percentile_approx": False, "approx_percentile": False}
+WINDOW_FUNCS = RANKING | OFFSET | VALUE | FRAMED_AGGS | set(FRAME_MOMENTS) | set(FRAME_SELECT)
 
 # The longest frame (rows) the one-launch two-pass kernel takes; longer frames go level by level.  The longest
 # measured frame at which the direct entry was no slower than the levels entry for every state kind
 # (profiles/window_frames/README.md).
 FRAME_DIRECT_MAX = 48
+# The longest frame (rows) the one-launch candidate-ranking kernel of window_select.hip takes; longer frames go
+# through the wavelet matrix (profiles/window_percentile/README.md).
+FRAME_SELECT_DIRECT_MAX = 32
+SELECT_MAX_RANKS = 16          # ranks per call of the selection entry points
 
 _INT_TYPES = ("byte", "short", "int", "integer", "long", "bigint", "tinyint", "smallint")
 _FLOAT_TYPES = ("float", "double")
@@ -296,6 +315,11 @@ def _compute(name, wc, ev, perm, idx, pstart, pend, peer_new, peer_start, peer_e
             out = _select_by_conditions([PrimColumn("boolean", ok)], [out], dflt, n, dev)
         return out
 
+    if name in FRAME_SELECT:
+        x, ps, is_array = _percentile_args(name, wc, ev, perm)
+        a, b = _frame(wc, idx, pstart, pend, peer_start, peer_end, rkey)
+        return _frame_percentile(name, x, ps, is_array, a, b, n, dev)
+
     if name in FRAME_MOMENTS:
         cols = _moment_args(name, wc, ev, perm)
         a, b = _frame(wc, idx, pstart, pend, peer_start, peer_end, rkey)
@@ -497,6 +521,202 @@ def _frame_state_tensor(kind, x, y, valid, a, b, maxlen) -> torch.Tensor:
             level = _merge_states(kind, level, [torch.cat([w[step:], zero[:pad]]) for w in level])
         k += 1
     return torch.stack(acc)
+
+
+def _percentile_args(name, wc, ev, perm):
+    """The arguments of a percentile window call: the numeric argument column in sorted order, the percentages as
+    floats, and whether they came as ``array(...)``."""
+    from .column import ArrayColumn
+    from .decimal import is_decimal
+    args = wc.func.args
+    want = (1,) if name == "median" else (2,) if name == "percentile" else (2, 3)
+    if wc.func.star or len(args) not in want:
+        raise WindowError(f"wrong number of arguments to {name}")
+    x = materialize(ev(args[0]))
+    if isinstance(x, ConstColumn):
+        x = x.materialize()
+    if not isinstance(x, PrimColumn) or not (is_decimal(x.dtype) or x.dtype in _INT_TYPES + _FLOAT_TYPES):
+        raise WindowError(f"{name} OVER needs a numeric argument")
+    if len(args) == 3 and not isinstance(ev(args[2]), ConstColumn):
+        raise WindowError(f"{name} accuracy must be a constant")             # accepted and ignored, as in GROUP BY
+    if name == "median":
+        return x.take(perm), [0.5], False
+    p = ev(args[1])
+    is_array = isinstance(p, ArrayColumn)
+    consts = p.elements if is_array else [p]
+    if not consts or not all(isinstance(c, ConstColumn) and c.value is not None for c in consts):
+        raise WindowError(f"{name} percentage must be a constant or an array of constants")
+    try:
+        ps = [float(c.value) for c in consts]
+    except (TypeError, ValueError):
+        raise WindowError(f"{name} percentage must be a constant or an array of constants") from None
+    if not all(0.0 <= q <= 1.0 for q in ps):
+        raise WindowError("percentile must be in [0, 1]")
+    return x.take(perm), ps, is_array
+
+
+def _frame_percentile(name, x, ps, is_array, a, b, n, dev):
+    """percentile / median / percentile_approx of ``x`` (sorted order) over the frames ``[a, b]`` for every
+    percentage of ``ps``: GROUP BY's ranks on the frame's count of non-NULL rows, the rows at those ranks from
+    ``_frame_select`` (all ranks of the call at once), then a gather — and, for the exact form, GROUP BY's
+    interpolation on doubles (decimals through ``decimal.to_double``).  The approximate form returns an input value,
+    so it keeps ``x``'s type."""
+    from ..ops.sort import column_order_key
+    from .column import ArrayColumn
+    from .decimal import is_decimal, to_double
+    from .query import _take_nullable, percentile_interpolate, percentile_ranks
+    exact = FRAME_SELECT[name]
+    key, valid = column_order_key(x)
+    nonempty = a <= b
+    vz = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(valid.to(torch.int64), 0)])
+    cnt = torch.where(nonempty, vz[(b + 1).clamp(0, n)] - vz[a.clamp(0, n)], torch.zeros_like(a))
+    has = cnt > 0
+    plans = [percentile_ranks(q, cnt, exact) for q in ps]
+    ranks = [r for plan in plans for r in plan[:2]]          # (lo, hi) per percentage, or (k,)
+    length = torch.where(nonempty, b - a + 1, torch.zeros_like(a))
+    maxlen = int(length.max())                               # one host read: the path choice
+    at = _frame_select(key, valid, vz, a, b, ranks, maxlen)
+    if exact:
+        xd = to_double(x) if is_decimal(x.dtype) else PrimColumn("double", x.data.to(torch.float64), x.valid)
+    out = []
+    for j, plan in enumerate(plans):
+        if exact:
+            vl = _take_nullable(xd, at[2 * j]).data
+            vh = _take_nullable(xd, at[2 * j + 1]).data
+            out.append(PrimColumn("double", percentile_interpolate(vl, vh, plan[2]), has))
+        else:
+            out.append(_take_nullable(x, at[j]))             # -1 (no counted row): NULL
+    if is_array:
+        return ArrayColumn(out, n, None, False, dev)
+    return out[0]
+
+
+def _frame_select(key, valid, vz, a, b, ranks, maxlen):
+    """For every rank tensor ``k`` of ``ranks``: the position of the ``k[i]``-th smallest counted row (0-based) of
+    the frame ``[a[i], b[i]]`` (clipped to [0, n); ``a > b``: empty) in (``key`` unsigned, position) order, or -1
+    where ``k[i]`` is negative or not below the frame's count.  ``key`` is one order-key word per row, ``valid`` the
+    counted rows, ``vz`` their exclusive prefix count (n + 1 entries), ``maxlen`` the longest frame length.  Native
+    on the GPU — ``SELECT_MAX_RANKS`` ranks per call — tensor operations on the CPU."""
+    if maxlen == 0:
+        return [torch.full_like(a, -1) for _ in ranks]
+    if not N.use_native(key):
+        return _frame_select_tensor(key, valid, vz, a, b, ranks)
+    out = []
+    tree = None
+    for s in range(0, len(ranks), SELECT_MAX_RANKS):
+        chunk = ranks[s:s + SELECT_MAX_RANKS]
+        if maxlen <= FRAME_SELECT_DIRECT_MAX:
+            out += _frame_select_direct(key, valid, a, b, chunk)
+        else:
+            tree = tree or _wavelet_build(key, valid)
+            out += _frame_select_tree(tree, vz, a, b, chunk)
+    return out
+
+
+def _frame_select_direct(key, valid, a, b, ranks):
+    n, m = int(key.shape[0]), len(ranks)
+    k = torch.stack(ranks).contiguous()
+    out = torch.empty((m, n), dtype=torch.int64, device=key.device)
+    N.call("dxa_frame_select_direct", N.ptr(key.contiguous()), N.ptr(N.u8(valid).contiguous()), N.ptr(a.contiguous()),
+           N.ptr(b.contiguous()), n, N.ptr(k), m, N.ptr(out), N.stream_handle(key.device))
+    return list(out.unbind(0))
+
+
+def _frame_select_tree(tree, vz, a, b, ranks):
+    Z, perm = tree
+    n, m = int(perm.shape[0]), len(ranks)
+    k = torch.stack(ranks).contiguous()
+    out = torch.empty((m, n), dtype=torch.int64, device=perm.device)
+    N.call("dxa_frame_select_tree", N.ptr(Z), N.ptr(perm), N.ptr(vz.contiguous()), N.ptr(a.contiguous()),
+           N.ptr(b.contiguous()), n, int(Z.shape[0]), N.ptr(k), m, N.ptr(out), N.stream_handle(perm.device))
+    return list(out.unbind(0))
+
+
+def _select_order(key, valid):
+    """(perm, r): the stable sort permutation of the rows by (not counted, key unsigned) and its inverse, every
+    row's global rank."""
+    from ..ops.sort import argsort_words
+    perm = argsort_words([key, (~valid).to(torch.int64)])
+    r = torch.empty_like(perm)
+    r[perm] = torch.arange(perm.shape[0], dtype=torch.int64, device=perm.device)
+    return perm, r
+
+
+def _wavelet_build(key, valid):
+    """The wavelet matrix of window_select.hip over the rows' global ranks → (Z int32 [L, n + 1], perm): per level
+    one prefix count of the zero bits (``torch.cumsum``) and one HIP launch that scatters the ranks into the next
+    level's ordering and writes that level's zero flags.  No host read besides the radix sort's own."""
+    perm, r = _select_order(key, valid)
+    n = int(r.shape[0])
+    dev = r.device
+    L = (n - 1).bit_length()
+    Z = torch.zeros((L, n + 1), dtype=torch.int32, device=dev)
+    if L == 0:
+        return Z, perm
+    cur = r.to(torch.int32)
+    nxt = torch.empty_like(cur)
+    flags = ((cur >> (L - 1)) & 1) ^ 1
+    st = N.stream_handle(dev)
+    for lev in range(L):
+        torch.cumsum(flags, 0, dtype=torch.int32, out=Z[lev, 1:])
+        bit = L - 1 - lev
+        if bit:
+            N.call("dxa_wavelet_level", N.ptr(cur), N.ptr(Z[lev]), n, bit, N.ptr(nxt), N.ptr(flags), st)
+            cur, nxt = nxt, cur
+    return Z, perm
+
+
+def _wavelet_build_tensor(key, valid):
+    """``_wavelet_build`` as tensor operations on any device."""
+    perm, cur = _select_order(key, valid)
+    n = int(cur.shape[0])
+    L = (n - 1).bit_length()
+    Z = torch.zeros((L, n + 1), dtype=torch.int32, device=cur.device)
+    idx = torch.arange(n, dtype=torch.int64, device=cur.device)
+    for lev in range(L):
+        bit = L - 1 - lev
+        zero = ((cur >> bit) & 1) == 0
+        zc = torch.cumsum(zero.to(torch.int64), 0)
+        Z[lev, 1:] = zc.to(torch.int32)
+        if bit:
+            before = zc - zero.to(torch.int64)               # zeros among the earlier elements
+            dst = torch.where(zero, before, zc[-1] + idx - before)
+            nxt = torch.empty_like(cur)
+            nxt[dst] = cur                                   # a stable partition: zeros first
+            cur = nxt
+    return Z, perm
+
+
+def _frame_select_tensor(key, valid, vz, a, b, ranks, tree=None):
+    """``_frame_select`` as vectorised tensor operations on any device — the wavelet-matrix walk of
+    ``dxa_frame_select_tree``: per level, with c0 = Z[hi1] − Z[lo] zeros in the range, a rank below c0 goes left
+    (lo = Z[lo], hi1 = Z[hi1]), else right (k −= c0, lo = z + lo − Z[lo], hi1 = z + hi1 − Z[hi1]); the bits taken
+    are the answer's global rank, which the sort permutation turns into a row position."""
+    Z, perm = tree if tree is not None else _wavelet_build_tensor(key, valid)
+    n = int(perm.shape[0])
+    lo, hi1 = a.clamp(min=0), (b + 1).clamp(max=n)           # frames are clipped to [0, n)
+    empty = (a > b) | (lo >= hi1)
+    lo = torch.where(empty, torch.zeros_like(lo), lo)
+    hi1 = torch.where(empty, torch.zeros_like(hi1), hi1)
+    cnt = vz[hi1] - vz[lo]
+    Z = Z.to(torch.int64)
+    out = []
+    for k in ranks:
+        ok = (k >= 0) & (k < cnt)
+        zero = torch.zeros_like(lo)
+        l, h, kk = torch.where(ok, lo, zero), torch.where(ok, hi1, zero), torch.where(ok, k, zero)
+        rank = zero
+        for lev in range(Z.shape[0]):
+            z = Z[lev]
+            zl, zh = z[l], z[h]
+            c0 = zh - zl
+            left = kk < c0
+            l = torch.where(left, zl, z[n] + l - zl)
+            h = torch.where(left, zh, z[n] + h - zh)
+            kk = torch.where(left, kk, kk - c0)
+            rank = rank * 2 + (~left).to(torch.int64)
+        out.append(torch.where(ok, perm[rank.clamp(max=n - 1)], torch.full_like(rank, -1)))
+    return out
 
 
 def _float_frame_sum(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, nonempty: torch.Tensor) -> torch.Tensor:
