@@ -145,8 +145,6 @@ __device__ __forceinline__ GArgs to_global(const ParseArgs& p) {
 
 __constant__ uint64_t kPow10i[9] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
                                     100000000ull};
-__constant__ double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                                  1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
 
 
 // Schema tables (node info, key texts, key lookup table) as seen by the parse loop.  With LDS=true the workgroup
@@ -474,11 +472,13 @@ __device__ __forceinline__ int64_t unescape_inplace(Reader& r, int64_t s, int64_
 
 // Run of decimal digits at r.p, accumulated into (mant, nd, exp10) exactly as a digit-serial loop would: at most
 // 19 significant digits kept (leading zeros are not significant); integer-part digits beyond that raise exp10 and
-// set `lost`; fraction digits beyond it are dropped.  Eight characters per step (SWAR digit test + conversion).
+// set `lost`; the next 19 digits go to (tail, nt) and a non-zero digit after those sets `sticky`, for the rounding
+// of doubles (decimal_dd.h).  Eight characters per step (SWAR digit test + conversion).
 // `first`: the run's first character; `term`: the character that ended it when the last compared word holds it
 // (256 otherwise: the record's end, or a word boundary).
 __device__ __forceinline__ bool scan_digits(Reader& r, uint64_t& mant, int& nd, int& exp10, bool& lost, bool frac,
-                                            uint64_t& tail, int& nt, uint32_t& first, uint32_t& term) {
+                                            uint64_t& tail, int& nt, bool& sticky, uint32_t& first,
+                                            uint32_t& term) {
   bool any = false;
   term = 256u;
   while (r.p < r.end) {
@@ -517,6 +517,7 @@ __device__ __forceinline__ bool scan_digits(Reader& r, uint64_t& mant, int& nd, 
         } else {
           if (!frac) { ++exp10; lost = true; }
           if (nt < 19) { tail = tail * 10 + (c - '0'); ++nt; }   // the next 19 digits, for the rounding
+          else sticky |= c != '0';
         }
       }
       r.p += k;
@@ -534,18 +535,18 @@ __device__ __forceinline__ bool scan_number(Reader& r, uint32_t c, bool& is_int,
   if (c == '-') { neg = true; ++r.p; }
   uint64_t mant = 0, tail = 0;
   int nd = 0, exp10 = 0, nt = 0;
-  bool lost = false;
+  bool lost = false, sticky = false;
   is_int = true;
   const int64_t s0 = r.p;
   uint32_t first = 0;
-  if (!scan_digits(r, mant, nd, exp10, lost, false, tail, nt, first, term)) return false;
+  if (!scan_digits(r, mant, nd, exp10, lost, false, tail, nt, sticky, first, term)) return false;
   if (first == '0' && r.p - s0 > 1) return false;                                     // JSON: no leading zeros
   if (term == 256u) term = r.cur();
   if (term == '.') {
     is_int = false;
     ++r.p;
     uint32_t f2;
-    if (!scan_digits(r, mant, nd, exp10, lost, true, tail, nt, f2, term)) return false;
+    if (!scan_digits(r, mant, nd, exp10, lost, true, tail, nt, sticky, f2, term)) return false;
     if (term == 256u) term = r.cur();
   }
   if ((term | 0x20u) == 'e') {
@@ -572,14 +573,8 @@ __device__ __forceinline__ bool scan_number(Reader& r, uint32_t c, bool& is_int,
     iv = neg ? (int64_t)(0ull - mant) : (int64_t)mant;
   }
   double d = (double)mant;
-  if (exp10 != 0 || mant >= (1ull << 53) || tail != 0) {
-    if (tail == 0 && mant < (1ull << 53) && exp10 > 0 && exp10 <= 22) d = d * kPow10[exp10];   // exact operands
-    else if (tail == 0 && mant < (1ull << 53) && exp10 < 0 && exp10 >= -22) d = d / kPow10[-exp10];
-    else if (mant == 0) d = 0.0;
-    else if (exp10 > DXA_POW10_DD_MAX) d = __builtin_inf();
-    else if (exp10 < DXA_POW10_DD_MIN) d = 0.0;
-    else d = dxa_decimal_to_double(mant, exp10, tail, nt);
-  }
+  if (exp10 != 0 || mant >= (1ull << 53) || tail != 0 || sticky)
+    d = dxa_decimal_to_double(mant, exp10, tail, nt, sticky, (const uint8_t*)(r.buf + s0), (int)(r.p - s0));
   dv = neg ? -d : d;
   return true;
 }
@@ -837,8 +832,10 @@ __device__ __forceinline__ bool parse_iso_ts(Reader& rd, int64_t s, int64_t e, i
   return true;
 }
 
-// Occupancy: with the LDS window the kernel needs ~103 VGPRs; amdgpu_waves_per_eu(5) caps it at 96 (2 dwords
-// spilled on cold paths) for 5 waves per SIMD (LDS: 25 KiB per 256-lane workgroup).  Bench batch (2 M events,
+// Occupancy: with the LDS window the kernel needs ~103 VGPRs; amdgpu_waves_per_eu(5) caps it at 96 (7 dwords
+// spilled on cold paths) for 5 waves per SIMD (LDS: 25 KiB per 256-lane workgroup).  Its 300 B of scratch per lane
+// are the two 32-limb integers of the cold noinline dxa_dd::resolve (decimal_dd.h), touched only by a number whose
+// rounding the double-double estimate cannot decide.  Bench batch (2 M events,
 // profiles/parse/parse_variants.md): register window 2.29 ms; LDS window 4 waves 1.76 ms; 5 waves 1.59 ms; 6 waves
 // 1.76 ms (12 dwords spilled); top-up threshold 48/40/32/24/16/1 bytes -> 1.72/1.64/1.58/1.58/1.66/1.73 ms.
 constexpr uint32_t kTopUp = 32;

@@ -765,8 +765,6 @@ __device__ __forceinline__ bool ci_eq(const uint8_t* s, int32_t l, const char* w
 __global__ void str_to_num_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ starts,
                                   const int32_t* __restrict__ lens, const uint8_t* __restrict__ valid, int64_t n,
                                   int32_t mode, int64_t* __restrict__ out, uint8_t* __restrict__ out_ok) {
-  const double kP10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15,
-                           1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     out[i] = 0;
     out_ok[i] = 0;
@@ -794,10 +792,16 @@ __global__ void str_to_num_kernel(const uint8_t* __restrict__ arena, const int64
     }
     uint64_t mant = 0, tail = 0;                          // first 19 significant digits, the next 19
     int nd = 0, exp10 = 0, digits = 0, nt = 0;
-    bool lost = false;
+    bool lost = false, sticky = false;                    // sticky: a non-zero digit after those 38
+    const int32_t p0 = p;
     for (; p < b && s[p] - '0' < 10u; ++p, ++digits) {
       if (nd < 19) { mant = mant * 10 + (s[p] - '0'); if (mant) ++nd; }
-      else { ++exp10; lost = true; if (nt < 19) { tail = tail * 10 + (s[p] - '0'); ++nt; } }
+      else {
+        ++exp10;
+        lost = true;
+        if (nt < 19) { tail = tail * 10 + (s[p] - '0'); ++nt; }
+        else sticky |= s[p] != '0';
+      }
     }
     int fdigits = 0;
     if (p < b && s[p] == '.') {
@@ -806,6 +810,7 @@ __global__ void str_to_num_kernel(const uint8_t* __restrict__ arena, const int64
         if (mode != 2) continue;
         if (nd < 19) { mant = mant * 10 + (s[p] - '0'); if (mant) ++nd; --exp10; }
         else if (nt < 19) { tail = tail * 10 + (s[p] - '0'); ++nt; }
+        else sticky |= s[p] != '0';
       }
     }
     if (digits + fdigits == 0) continue;
@@ -821,13 +826,7 @@ __global__ void str_to_num_kernel(const uint8_t* __restrict__ arena, const int64
     }
     if (p != b) continue;                                 // trailing garbage
     if (mode == 2) {
-      double d = (double)mant;
-      if (mant == 0) d = 0.0;
-      else if (tail == 0 && mant < (1ull << 53) && exp10 >= 0 && exp10 <= 22) d = d * kP10[exp10];
-      else if (tail == 0 && mant < (1ull << 53) && exp10 < 0 && exp10 >= -22) d = d / kP10[-exp10];
-      else if (exp10 > DXA_POW10_DD_MAX) d = __builtin_inf();
-      else if (exp10 < DXA_POW10_DD_MIN) d = 0.0;
-      else d = dxa_decimal_to_double(mant, exp10, tail, nt);
+      const double d = dxa_decimal_to_double(mant, exp10, tail, nt, sticky, s + p0, b - p0);
       out[i] = __double_as_longlong(neg ? -d : d);
       out_ok[i] = 1;
       continue;
@@ -847,6 +846,21 @@ DXA_API int dxa_str_to_num(const uint8_t* arena, const int64_t* starts, const in
   hipLaunchKernelGGL(str_to_num_kernel, dim3(dxa_blocks(n, 256)), dim3(256), 0, (hipStream_t)st, arena, starts, lens,
                      valid, n, mode, out, out_ok);
   return (int)hipGetLastError();
+}
+
+// The same __host__ __device__ conversion run on the CPU (no GPU needed) — lets CPU tests pin the device algorithm.
+// Case i is (head, e10, tail, nt, sticky) as the digit scanners deliver them, with its text (from the first digit)
+// at text[offs[i], offs[i + 1]); exact[i] tells whether the exact path decided.
+DXA_API int dxa_decimal_to_double_hostcheck(const uint64_t* head, const int32_t* e10, const uint64_t* tail,
+                                            const int32_t* nt, const uint8_t* sticky, const uint8_t* text,
+                                            const int64_t* offs, int64_t n, double* out, uint8_t* exact) {
+  for (int64_t i = 0; i < n; ++i) {
+    int ex = 0;
+    out[i] = dxa_decimal_to_double(head[i], e10[i], tail[i], nt[i], sticky[i] != 0, text + offs[i],
+                                   (int)(offs[i + 1] - offs[i]), &ex);
+    exact[i] = (uint8_t)ex;
+  }
+  return 0;
 }
 
 // General LIKE on the device.  Pattern tokens (int16): 0..255 a literal byte, 256 '_' (one UTF-8 character),

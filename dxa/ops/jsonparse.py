@@ -515,7 +515,10 @@ def _convert(v, dtype):
     if dtype in ("double", "float", "decimal"):
         if isinstance(v, bool) or not isinstance(v, (int, float, _Decimal)):
             return None
-        return float(v)
+        try:
+            return float(v)
+        except OverflowError:                          # an integer token past DBL_MAX: infinity, as parseDouble
+            return float("inf") if v > 0 else float("-inf")
     if dtype == "string" and isinstance(v, _Decimal):
         return str(v)                                  # the number token's own text
     v = _floats(v)

@@ -90,6 +90,7 @@ _SIGS = {
     "dxa_f64_str_len": [c_p, c_p, c_i64, c_p, c_p],
     "dxa_f64_str_write": [c_p, c_p, c_i64, c_p, c_p, c_p],
     "dxa_str_to_num": [c_p, c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_p],
+    "dxa_decimal_to_double_hostcheck": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p],
     "dxa_concat_ws_len": [c_p, c_i32, c_i64, c_i32, c_p, c_p],
     "dxa_concat_ws_write": [c_p, c_i32, c_i64, c_p, c_i32, c_p, c_p, c_p],
     "dxa_str_substr": [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p],

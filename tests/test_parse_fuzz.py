@@ -150,9 +150,11 @@ def _json_number(rnd):
 
 
 def test_gpu_number_text_matches_reference(gpu):
-    """Decimal text → double / long over long mantissas and exponents past both ends of the double range."""
+    """Decimal text → double / long over long mantissas and exponents past both ends of the double range.  Each pair
+    of texts is parsed both ways round, so every text is read once as a double and once as a long."""
     rnd = random.Random(5)
-    recs = [('{"b":%s,"a":%s}' % (_json_number(rnd), _json_number(rnd))).encode() for _ in range(20000)]
+    pairs = [(_json_number(rnd), _json_number(rnd)) for _ in range(20000)]
+    recs = [('{"b":%s,"a":%s}' % p).encode() for p in pairs] + [('{"b":%s,"a":%s}' % p[::-1]).encode() for p in pairs]
     plan = ParsePlan(SCHEMA)
     cpu_raw, cpu_ok = parse(*frame_records(recs), plan)
     gpu_raw, gpu_ok = parse(*frame_records(recs, device=gpu), plan)
