@@ -15,6 +15,7 @@ import torch
 
 from ..ops import groupby as G
 from ..ops import join as J
+from ..ops import native as N
 from .. import parallel as P
 from ..ops.hashing import hash_columns
 from ..sql import ast as A
@@ -1931,8 +1932,127 @@ def _percentile(groups: G.Groups, arg, p, exact: bool):
     return PrimColumn(arg.dtype if arg.dtype in ("double", "float") else "double", r, has)
 
 
+# collect_list / collect_set keep K slots for every group, K the longest group: K · ngroups is the size of the result
+# itself.  Past this many slots the call is refused instead of allocated (a guard, not a tuned number).
+COLLECT_MAX_SLOTS = 1 << 28
+
+
+def collectable(arg) -> bool:
+    """True for the arguments whose collected arrays are slot matrices over the argument's own words: every
+    primitive column (one- and two-lane decimals, boolean, date, timestamp included) and strings.  Struct, array, map
+    and binary arguments render as JSON text on the host (``_collect_host``)."""
+    from .column import JsonColumn
+    return (isinstance(arg, (PrimColumn, StrColumn)) and not isinstance(arg, JsonColumn)
+            and isinstance(arg.dtype, str) and arg.dtype not in ("binary", "null"))
+
+
 def _collect(groups: G.Groups, arg, as_set):
-    """collect_list/collect_set → JSON array text per group (host-assisted)."""
+    """collect_list / collect_set per group: an array column, never NULL, empty for a group with no non-NULL
+    argument; the list in input order, the set in first-occurrence order with the first occurrence's bits."""
+    if collectable(arg):
+        return _collect_slots(groups, arg, as_set)
+    return _collect_host(groups, arg, as_set)
+
+
+def slot_leaves(arg) -> List[torch.Tensor]:
+    """The 1-D word tensors a slot of ``arg`` is made of: string starts / lens, a wide decimal's lo / hi lanes, or
+    the data."""
+    if isinstance(arg, StrColumn):
+        return [arg.starts, arg.lens]
+    if arg.data.dim() == 2:
+        return [arg.data[:, 0].contiguous(), arg.data[:, 1].contiguous()]
+    return [arg.data]
+
+
+def array_from_slots(arg, mats, n: int, valid, present) -> ArrayColumn:
+    """The array column over ``n`` rows whose slot k is row k of every ``[K, n]`` leaf matrix in ``mats`` (the leaves
+    of ``slot_leaves(arg)``), shaped as ``sqlfuncs.array_from_pylist`` shapes it: where the rows' lengths differ a
+    ``present`` mask [n, K] and slot validity ``valid`` [K, n], else neither; with no slot at all (``mats`` None) one
+    all-NULL slot that no row has."""
+    dev = arg.device
+    if mats is None:
+        if isinstance(arg, StrColumn):
+            null = StrColumn(arg.arena, torch.zeros(n, dtype=torch.int64, device=dev),
+                             torch.zeros(n, dtype=torch.int32, device=dev),
+                             torch.zeros(n, dtype=torch.bool, device=dev), arg.dtype)
+        else:
+            null = PrimColumn(arg.dtype, torch.zeros((n,) + tuple(arg.data.shape[1:]), dtype=arg.data.dtype,
+                                                     device=dev), torch.zeros(n, dtype=torch.bool, device=dev))
+        return ArrayColumn([null], n, None, False, dev, present=torch.zeros((n, 1), dtype=torch.bool, device=dev))
+    K = int(mats[0].shape[0])
+    if isinstance(arg, StrColumn):
+        def slot(k, v):
+            c = type(arg)(arg.arena, mats[0][k], mats[1][k], v, arg.dtype)
+            c.max_len = arg.max_len
+            return c
+    elif arg.data.dim() == 2:
+        wide = torch.stack(mats, 2)                              # [K, n, (lo, hi)]
+
+        def slot(k, v):
+            return PrimColumn(arg.dtype, wide[k], v)
+    else:
+        def slot(k, v):
+            return PrimColumn(arg.dtype, mats[0][k], v)
+    els = [slot(k, None if valid is None else valid[k]) for k in range(K)]
+    return ArrayColumn(els, n, None, False, dev, present=present)
+
+
+def _collect_slots(groups: G.Groups, arg, as_set):
+    """``_collect`` for a primitive or string argument, on any device.  The rows that count — the non-NULL rows,
+    for the set those that are the first row of their (group, value) pair by GROUP BY's own equality (every NaN
+    one value, -0.0 equal to 0.0) — are brought into (group, input position) order by one stable radix argsort of
+    their group ids; slot k of group g is then the k-th of the group's rows.  On the GPU one launch of
+    ``dxa_collect_scatter`` writes every leaf's ``[K, ngroups]`` slot matrix and the masks; on a CPU device the same
+    matrices come from tensor operations.  One host read: the longest and the shortest group."""
+    from ..ops.sort import argsort_words
+    name = "collect_set" if as_set else "collect_list"
+    dev = arg.device
+    ng, n = groups.ngroups, arg.length
+    gid = groups.gid.to(torch.int64)
+    ok = arg.valid_mask()
+    if as_set and n:
+        first = torch.zeros(n, dtype=torch.bool, device=dev)
+        first[G.group_rows([PrimColumn("long", gid), arg]).rep] = True
+        ok = ok & first
+    rows = torch.nonzero(ok).flatten()
+    g = gid[rows]
+    cnt = torch.bincount(g, minlength=ng)
+    K, kmin = torch.stack([cnt.max(), cnt.min()]).tolist() if ng else (0, 0)
+    if K * ng > COLLECT_MAX_SLOTS:
+        raise QueryError(f"{name}: {ng} groups of up to {K} elements need {K * ng} slots, more than "
+                         f"COLLECT_MAX_SLOTS ({COLLECT_MAX_SLOTS})")
+    if K == 0:
+        return array_from_slots(arg, None, ng, None, None)
+    srows = rows[argsort_words([g])]
+    start = torch.cumsum(cnt, 0) - cnt
+    leaves = slot_leaves(arg)
+    ragged = kmin != K
+    if N.use_native(srows):
+        import ctypes
+        mats = [torch.empty((K, ng), dtype=t.dtype, device=dev) for t in leaves]
+        valid = torch.empty((K, ng), dtype=torch.bool, device=dev) if ragged else None
+        present = torch.empty((ng, K), dtype=torch.bool, device=dev) if ragged else None
+        srcs = [t.contiguous() for t in leaves]
+        nl = len(srcs)
+        sp = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in srcs])
+        dp = (ctypes.c_void_p * nl)(*[t.data_ptr() for t in mats])
+        el = (ctypes.c_int32 * nl)(*[t.element_size() for t in srcs])
+        N.call("dxa_collect_scatter", N.ptr(srows), int(srows.shape[0]), N.ptr(start), N.ptr(cnt), ng, K,
+               ctypes.cast(sp, ctypes.c_void_p), ctypes.cast(dp, ctypes.c_void_p), ctypes.cast(el, ctypes.c_void_p),
+               nl, n, N.ptr(valid), N.ptr(present), N.stream_handle(dev))
+    else:
+        k = torch.arange(K, dtype=torch.int64, device=dev)[:, None]
+        okm = k < cnt[None, :]
+        r = srows[(start[None, :] + k).clamp(max=int(srows.shape[0]) - 1)]
+        mats = [torch.where(okm, t[r], torch.zeros((), dtype=t.dtype, device=dev)) for t in leaves]
+        valid = okm if ragged else None
+        present = okm.t().contiguous() if ragged else None
+    return array_from_slots(arg, mats, ng, valid, present)
+
+
+def _collect_host(groups: G.Groups, arg, as_set):
+    """collect_list / collect_set row by row on the host: struct, array, map and binary arguments (→ JSON array text
+    per group), and the oracle of the device path's tests."""
     from .column import strings_from_pylist
     import json
     from .serialize import json_value

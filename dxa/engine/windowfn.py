@@ -40,6 +40,10 @@ every statement to ``spark.sql``); here each window call is evaluated column-at-
    that counts, per row, the frame's global ranks below a threshold; on a CPU device the same walk runs as tensor
    operations (``_frame_distinct_tensor``).  A previous occurrence in another partition lies before the frame, so
    neither path has a partition case;
+   ``collect_list(x)`` / ``collect_set(x)`` give the frame's counted values as an array, never NULL, in the frame's
+   sorted order — the set at every value's first row inside the frame, the rows with p[j] < a of the same array p —
+   as a ``[K, n]`` matrix of row positions, K the largest per-frame count, from ``ops/csrc/collect.hip``
+   (``dxa_frame_collect``, one launch) or, on a CPU device, tensor operations; one gather builds the elements;
 4. the result is scattered back to input row order.
 
 Known caveat, shared with GROUP BY: ``M2 > 0`` is tested on a rounded M2, so corr / skewness / kurtosis of a constant
@@ -84,7 +88,10 @@ FRAME_SELECT = {"percentile": True, "median": True, "percentile_approx": False, 
 # distinct counts over a frame: approx_count_distinct(x[, rsd]) (exact here, as in GROUP BY) and count(DISTINCT …)
 COUNT_DISTINCT = "count(DISTINCT …)"                    # the evaluator's own name for count(DISTINCT a, …)
 FRAME_DISTINCT = {"approx_count_distinct", COUNT_DISTINCT}
-WINDOW_FUNCS = RANKING | OFFSET | VALUE | FRAMED_AGGS | set(FRAME_MOMENTS) | set(FRAME_SELECT) | FRAME_DISTINCT
+# the frame's counted values as an array: the list in the frame's sorted order, the set at every value's first row
+FRAME_COLLECT = {"collect_list", "collect_set"}
+WINDOW_FUNCS = (RANKING | OFFSET | VALUE | FRAMED_AGGS | set(FRAME_MOMENTS) | set(FRAME_SELECT) | FRAME_DISTINCT
+                | FRAME_COLLECT)
 
 # The longest frame (rows) the one-launch two-pass kernel takes; longer frames go level by level.  The longest
 # measured frame at which the direct entry was no slower than the levels entry for every state kind
@@ -99,6 +106,9 @@ SELECT_MAX_RANKS = 16          # ranks per call of the selection entry points
 # than the matrix build and query for both value cardinalities: 0.92–0.94 ms against 1.18–1.28 ms at 2,048 rows,
 # 1.38–1.40 ms against 1.18–1.23 ms at 4,096 (profiles/window_frame_distinct/README.md).
 FRAME_DISTINCT_DIRECT_MAX = 2048
+# collect_list / collect_set OVER keep K slots for every row, K the largest per-frame count: K · n is the size of the
+# result itself.  Past this many slots the call is refused instead of allocated (a guard, not a tuned number).
+FRAME_COLLECT_MAX_SLOTS = 1 << 27
 
 _INT_TYPES = ("byte", "short", "int", "integer", "long", "bigint", "tinyint", "smallint")
 _FLOAT_TYPES = ("float", "double")
@@ -160,10 +170,15 @@ def evaluate_window(wc: A.WindowCall, ev: Callable[[A.Expr], Column], n: int, de
         raise WindowError(f"{name} is not supported as a window function")
     # count(DISTINCT a, …) is the one DISTINCT a window takes (a superset of Spark, which refuses them all)
     if wc.func.distinct:
+        if name in FRAME_COLLECT:
+            raise WindowError(f"{name}(DISTINCT …) is not supported as a window function")
         if name != "count" or wc.func.star or not wc.func.args:
             raise WindowError("DISTINCT is not supported in window aggregates")
         name = COUNT_DISTINCT
     i64 = torch.int64
+    if n == 0 and name in FRAME_COLLECT:
+        from .query import array_from_slots
+        return array_from_slots(_collect_arg(name, wc, ev), None, 0, None, None)
     if n == 0:
         integral = name in RANKING - {"percent_rank", "cume_dist"} or name in FRAME_DISTINCT
         return ConstColumn(None, "long" if integral else "double", 0, dev)
@@ -351,6 +366,11 @@ def _compute(name, wc, ev, perm, idx, pstart, pend, peer_new, peer_start, peer_e
         vid, counted = _distinct_args(name, wc, ev, perm)
         a, b = _frame(wc, idx, pstart, pend, peer_start, peer_end, rkey)
         return PrimColumn("long", _frame_distinct(vid, counted, a, b))
+
+    if name in FRAME_COLLECT:
+        x = _collect_arg(name, wc, ev).take(perm)
+        a, b = _frame(wc, idx, pstart, pend, peer_start, peer_end, rkey)
+        return _frame_collect(name, x, a, b)
 
     if name in FRAME_MOMENTS:
         cols = _moment_args(name, wc, ev, perm)
@@ -799,16 +819,17 @@ def _prev_occurrence(vid, counted) -> torch.Tensor:
     return p
 
 
-def _frame_distinct(vid, counted, a, b) -> torch.Tensor:
+def _frame_distinct(vid, counted, a, b, p=None) -> torch.Tensor:
     """The number of different value ids among the counted rows of every frame ``[a[i], b[i]]`` (clipped to [0, n);
-    ``a > b``: empty, 0) as int64: with ``p`` the previous-occurrence array, #{ j in the frame : p[j] < a[i] }.  Native
-    on the GPU — a linear scan of ``p`` when the longest frame is at most ``FRAME_DISTINCT_DIRECT_MAX`` rows, else a
-    wavelet matrix over ``p`` — tensor operations on the CPU."""
+    ``a > b``: empty, 0) as int64: with ``p`` the previous-occurrence array (computed here unless the caller has it),
+    #{ j in the frame : p[j] < a[i] }.  Native on the GPU — a linear scan of ``p`` when the longest frame is at most
+    ``FRAME_DISTINCT_DIRECT_MAX`` rows, else a wavelet matrix over ``p`` — tensor operations on the CPU."""
     length = torch.where(a <= b, b - a + 1, torch.zeros_like(a))
     maxlen = int(length.max())                               # one host read: the path choice
     if maxlen == 0:
         return torch.zeros_like(a)
-    p = _prev_occurrence(vid, counted)
+    if p is None:
+        p = _prev_occurrence(vid, counted)
     if not N.use_native(p):
         return _frame_distinct_tensor(p, counted, a, b)
     if maxlen <= FRAME_DISTINCT_DIRECT_MAX:
@@ -877,6 +898,101 @@ def _frame_distinct_tensor(p, counted, a, b, tree=None):
         l = torch.where(right, z[n] + l - zl, zl)
         h = torch.where(right, z[n] + h - zh, zh)
     return torch.where(empty, zero, torch.where(whole, hi1 - lo, count))
+
+
+def _collect_arg(name, wc, ev):
+    """The one argument of collect_list / collect_set OVER, in input order: a primitive or string column (the types
+    GROUP BY collects on the device, ``query.collectable``)."""
+    from .query import collectable
+    args = wc.func.args
+    if wc.func.star or len(args) != 1:
+        raise WindowError(f"{name} OVER takes one argument")
+    x = materialize(ev(args[0]))
+    if isinstance(x, ConstColumn):
+        x = x.materialize()
+    if not collectable(x):
+        raise WindowError(f"{name} OVER cannot collect values of type {x.dtype}")
+    return x
+
+
+def _frame_collect(name, x, a, b):
+    """collect_list / collect_set of ``x`` (sorted order) over every frame ``[a[i], b[i]]``: an array column, never
+    NULL, empty where the frame is empty or holds no counted (non-NULL) row.  Elements stand in the frame's sorted
+    order; the set keeps every value's first row inside the frame, by GROUP BY's equality (``G.group_rows``), so
+    its size is ``count(DISTINCT x)`` over the same frame.  The slots are a ``[K, n]`` matrix of sorted-order
+    positions (``_frame_collect_positions``), K the largest per-frame count — one host read beside the longest
+    frame — and the element columns one gather of ``x``'s leaves over the flattened matrix."""
+    from ..ops.gather import gather_many
+    from .query import array_from_slots, slot_leaves
+    n, dev = x.length, x.device
+    as_set = name == "collect_set"
+    counted = x.valid_mask()
+    length = torch.where(a <= b, b - a + 1, torch.zeros_like(a))
+    p = None
+    if as_set:
+        try:
+            vid = G.group_rows([x]).gid.to(torch.int64)
+        except TypeError as ex:
+            raise WindowError(f"{name} OVER cannot collect its argument: {ex}") from ex
+        p = _prev_occurrence(vid, counted)
+        cnt = _frame_distinct(vid, counted, a, b, p)
+    else:
+        pz = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counted.to(torch.int64), 0)])
+        cnt = torch.where(a <= b, pz[(b + 1).clamp(0, n)] - pz[a.clamp(0, n)], torch.zeros_like(a))
+    maxlen, K, kmin = torch.stack([length.max(), cnt.max(), cnt.min()]).tolist()
+    if K * n > FRAME_COLLECT_MAX_SLOTS:
+        raise WindowError(f"{name} OVER: the frame is too long to collect: {n} rows of up to {K} elements need "
+                          f"{K * n} slots, more than FRAME_COLLECT_MAX_SLOTS ({FRAME_COLLECT_MAX_SLOTS})")
+    if K == 0:
+        return array_from_slots(x, None, n, None, None)
+    pos = _frame_collect_positions(a, b, counted, p, K, maxlen)
+    flat = pos.reshape(-1)
+    leaves = slot_leaves(x)
+    if N.use_native(flat):
+        # gather_many reads an index outside [-n, n) as zero: the absent slots
+        mats = [t.view(K, n) for t in gather_many(leaves, torch.where(flat < 0, torch.full_like(flat, n), flat))]
+    else:
+        have = pos >= 0
+        at = pos.clamp(min=0)
+        mats = [torch.where(have, t[at], torch.zeros((), dtype=t.dtype, device=dev)) for t in leaves]
+    ragged = kmin != K
+    valid = (pos >= 0) if ragged else None
+    return array_from_slots(x, mats, n, valid, valid.t().contiguous() if ragged else None)
+
+
+def _frame_collect_positions(a, b, counted, p, K, maxlen) -> torch.Tensor:
+    """``[K, n]`` int64: row i's column holds, top down, the positions j in ``[a[i], b[i]]`` (clipped to [0, n)) with
+    ``counted[j]`` and — for the set, ``p`` the previous-occurrence array — ``p[j] < a[i]``; -1 below them.  Native
+    on the GPU (``dxa_frame_collect``: one launch, one thread per row; a wave-per-row shape was measured and was
+    never faster, profiles/collect/README.md); on a CPU device the list's positions come from the prefix count of
+    ``counted`` and the set's from a scan over the frame offsets."""
+    n, dev = int(a.shape[0]), a.device
+    if N.use_native(a):
+        out = torch.empty((K, n), dtype=torch.int64, device=dev)
+        N.call("dxa_frame_collect", N.ptr(a.contiguous()), N.ptr(b.contiguous()), N.ptr(N.u8(counted.contiguous())),
+               N.ptr(p), n, K, N.ptr(out), N.stream_handle(dev))
+        return out
+    lo, hi1 = a.clamp(min=0), (b + 1).clamp(max=n)             # frames are clipped to [0, n)
+    empty = (a > b) | (lo >= hi1)
+    zero = torch.zeros_like(lo)
+    lo, hi1 = torch.where(empty, zero, lo), torch.where(empty, zero, hi1)
+    if p is None:
+        pz = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counted.to(torch.int64), 0)])
+        cpos = torch.nonzero(counted).flatten()                # K > 0: at least one counted row
+        k = torch.arange(K, dtype=torch.int64, device=dev)[:, None]
+        have = k < (pz[hi1] - pz[lo])[None, :]
+        at = cpos[(pz[lo][None, :] + k).clamp(max=int(cpos.shape[0]) - 1)]
+        return torch.where(have, at, torch.full_like(at, -1))
+    out = torch.full((K, n), -1, dtype=torch.int64, device=dev)
+    s = torch.zeros_like(lo)
+    p64 = p.to(torch.int64)
+    for d in range(int(maxlen)):
+        j = lo + d
+        keep = (j < hi1) & (p64[j.clamp(max=n - 1)] < lo)      # a row that is not counted has p = n
+        r = torch.nonzero(keep).flatten()
+        out[s[r], r] = j[r]
+        s = s + keep.to(torch.int64)
+    return out
 
 
 def _float_frame_sum(x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, nonempty: torch.Tensor) -> torch.Tensor:

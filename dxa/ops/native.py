@@ -114,6 +114,9 @@ _SIGS = {
                             c_p],
     "dxa_datagen_write": [c_p, c_i32, c_p, c_i32, c_p, c_i32, ctypes.c_uint64, c_i64, c_i64, c_i64, c_i64, c_p,
                           c_p, c_p],
+    # collect.hip: collect_list / collect_set slot matrices, per group and per window frame
+    "dxa_collect_scatter": [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i64, c_p, c_p, c_p],
+    "dxa_frame_collect": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p],
 }
 
 # optional symbols (added by later kernels); bound if present
