@@ -150,9 +150,10 @@ def format_timestamp_us(us: int, iso: bool = True) -> str:
     """Spark ``to_json`` timestamp text (``yyyy-MM-dd'T'HH:mm:ss.SSSXXX`` in UTC) or CAST text
     (``yyyy-MM-dd HH:mm:ss[.fff]``)."""
     t = _dt.datetime(1970, 1, 1) + _dt.timedelta(microseconds=int(us))
+    year = f"{t.year:04d}"                  # strftime("%Y") does not pad years below 1000; Java's yyyy does
     if iso:
-        return t.strftime("%Y-%m-%dT%H:%M:%S.") + f"{t.microsecond // 1000:03d}Z"
-    s = t.strftime("%Y-%m-%d %H:%M:%S")
+        return year + t.strftime("-%m-%dT%H:%M:%S.") + f"{t.microsecond // 1000:03d}Z"
+    s = year + t.strftime("-%m-%d %H:%M:%S")
     if t.microsecond:
         s += ("." + f"{t.microsecond:06d}").rstrip("0")
     return s

@@ -180,6 +180,13 @@ class DevNode(ctypes.Structure):
                 ("lens", ctypes.c_void_p)]
 
 
+MAX_DEPTH = 30                       # the kernels keep the comma state of a row as one bit per level in a 32-bit word
+
+
+class PlanTooDeep(ValueError):
+    """A table nested deeper than the device serializer renders (the host serializer has no such limit)."""
+
+
 class _DevBuilder:
     """SerNode tree over *device* buffers for the GPU serializer (json_serialize.hip); names and constant values go
     into one text pool."""
@@ -279,8 +286,8 @@ class _DevBuilder:
     def _emit(self, ops: List[List[int]], idx: int, depth: int, mode: int):
         # a method, not a nested recursive function: that would be a reference cycle pinning this plan (and the
         # column tensors it keeps alive) until the cyclic collector ran
-        if depth > 30:
-            raise ValueError("JSON nesting deeper than 30 levels")
+        if depth > MAX_DEPTH:
+            raise PlanTooDeep(f"JSON nesting deeper than {MAX_DEPTH} levels")
         pos = len(ops)
         ops.append([0, idx, depth, mode])
         nd = self.nodes[idx]
@@ -318,14 +325,32 @@ def _render_members(members: List["Staged"]) -> None:
     """Render every GPU-staged table of ``members`` with ONE length launch, one scan, one write launch, one upload
     of the render tables and one D2H each for the lengths and the text (a segment per table); each member's
     ``JsonLines`` is a slice of the shared pinned blob.  A gzip member is rendered alone (its compressed stream is
-    what crosses PCIe)."""
+    what crosses PCIe).
+
+    The kernels stage the render tables in 64 KiB of LDS and track at most ``MAX_DEPTH`` nesting levels: members whose
+    real plan does not fit together render in two smaller groups, and a single member that is too wide or too deep
+    for the kernels at all is copied to the host and rendered by the host serializer."""
     from . import native as N
     dev = members[0].device
     side = _side_stream(dev)
     with torch.inference_mode(), torch.cuda.stream(side):
         for m in members:
             side.wait_event(m.event)
-        plan, keep = _plan_of(members)
+        try:
+            plan, keep = _plan_of(members)
+        except PlanTooDeep:
+            plan = None
+        if plan is None or len(plan[0]) > _LDS_LIMIT:
+            if len(members) > 1:
+                half = len(members) // 2
+                _render_members(members[:half])
+                _render_members(members[half:])
+            else:
+                b = _Builder()
+                top = [b.add(c, nm) for nm, c in zip(members[0].table.names, members[0].table.columns)]
+                side.synchronize()                      # the builder's D2H copies
+                members[0]._done(_render_host(b, top, members[0].n))
+            return
         blob, nnodes, nprog, tw, pcs = plan
         segs = _SerSegs()
         segs.nseg = len(members)
@@ -448,6 +473,30 @@ def _const_text(v, dtype) -> bytes:
             _CONST_TEXT.clear()
         t = _CONST_TEXT[key] = _scalar_text(v, dtype).encode("utf-8")
     return t
+
+
+def _const_bytes(v, dtype) -> int:
+    """Bytes of a constant's text in the pool."""
+    if type(v) in (str, int, float, bool):
+        return len(_const_text(v, dtype))
+    from ..engine.serialize import _scalar_text
+    return len(_scalar_text(v, dtype).encode("utf-8"))
+
+
+_NAME_BYTES: dict = {}
+
+
+def _name_bytes(name: Optional[str]) -> int:
+    """Bytes of a field name in the pool (quoted and escaped UTF-8 plus the colon), memoised: a batch's outputs
+    carry the same names every batch."""
+    if not name:
+        return 0
+    n = _NAME_BYTES.get(name)
+    if n is None:
+        if len(_NAME_BYTES) >= 4096:
+            _NAME_BYTES.clear()
+        n = _NAME_BYTES[name] = len(_quoted(name)) + 1
+    return n
 
 
 def _flat_pointers(members: List["Staged"], keep: list) -> List[int]:
@@ -653,14 +702,18 @@ class Staged:
         self.table = None
 
     def lds_estimate(self) -> int:
-        """Upper bound of this table's share of the render tables (nodes + program + names) in LDS."""
+        """Upper bound of this table's share of the render tables in LDS: per node the DevNode, a FIELD and a CLOSE
+        op, and its name and constant as the text pool holds them (quoted UTF-8, each padded to 8 bytes); a nested
+        node costs a second DevNode (``_DevBuilder.add`` builds it at the end, then moves it into its slot)."""
         def walk(c, name):
             kids = getattr(c, "children", None) or getattr(c, "elements", None) or []
             names = getattr(c, "names", None) or [None] * len(kids)
-            const = len(str(getattr(c, "value", "") or "")) if type(c).__name__ == "ConstColumn" else 0
-            return (ctypes.sizeof(DevNode) + 32 + len(name or "") + 16 + const +
+            const = 0
+            if type(c).__name__ == "ConstColumn" and c.value is not None:
+                const = _const_bytes(c.value, c.dtype)
+            return (ctypes.sizeof(DevNode) * (1 + len(kids)) + 32 + _name_bytes(name) + 16 + const +
                     sum(walk(k, nm) for nm, k in zip(names, kids)))
-        return sum(walk(c, nm) for nm, c in zip(self.table.names, self.table.columns))
+        return 16 + sum(walk(c, nm) for nm, c in zip(self.table.names, self.table.columns))
 
     def _render_gpu(self) -> "JsonLines":
         if self._result is None:
@@ -675,26 +728,31 @@ class Staged:
             return self._render_gpu()
         if self.event is not None:
             self.event.synchronize()
-        L = lib()
-        b = self.builder
-        arr = (SerNode * max(1, len(b.nodes)))()
-        for i, nd in enumerate(b.nodes):
-            arr[i] = SerNode(nd["kind"], nd["nchildren"], nd["child0"], nd["drop_nulls"], nd["name"],
-                             len(nd["name"]), 0, nd["data"], nd["valid"], nd["arena"], nd["starts"], nd["lens"],
-                             nd["const"], len(nd["const"]), 0)
-        tops = (ctypes.c_int32 * max(1, len(self.top)))(*self.top)
-        n = self.n
-        line_len = np.zeros(max(1, n), dtype=np.int64)
-        out_len = ctypes.c_int64(0)
-        threads = nthreads or min(16, os.cpu_count() or 4)
-        ptr = L.dxa_serialize_rows(ctypes.addressof(arr), len(b.nodes), ctypes.addressof(tops), len(self.top), n,
-                                   threads, line_len.ctypes.data, ctypes.addressof(out_len))
-        try:
-            blob = ctypes.string_at(ptr, out_len.value)
-        finally:
-            L.dxa_host_free(ptr)
+        jl = _render_host(self.builder, self.top, self.n, nthreads)
         self.builder = None                 # release pinned buffers
-        return JsonLines(blob, line_len[:n])
+        return jl
+
+
+def _render_host(b: _Builder, top: List[int], n: int, nthreads: Optional[int] = None) -> "JsonLines":
+    """The rows of a table described by ``b`` (host buffers, their copies complete) through the native host
+    serializer."""
+    L = lib()
+    arr = (SerNode * max(1, len(b.nodes)))()
+    for i, nd in enumerate(b.nodes):
+        arr[i] = SerNode(nd["kind"], nd["nchildren"], nd["child0"], nd["drop_nulls"], nd["name"],
+                         len(nd["name"]), 0, nd["data"], nd["valid"], nd["arena"], nd["starts"], nd["lens"],
+                         nd["const"], len(nd["const"]), 0)
+    tops = (ctypes.c_int32 * max(1, len(top)))(*top)
+    line_len = np.zeros(max(1, n), dtype=np.int64)
+    out_len = ctypes.c_int64(0)
+    threads = nthreads or min(16, os.cpu_count() or 4)
+    ptr = L.dxa_serialize_rows(ctypes.addressof(arr), len(b.nodes), ctypes.addressof(tops), len(top), n,
+                               threads, line_len.ctypes.data, ctypes.addressof(out_len))
+    try:
+        blob = ctypes.string_at(ptr, out_len.value)
+    finally:
+        L.dxa_host_free(ptr)
+    return JsonLines(blob, line_len[:n])
 
 
 class JsonLines:
